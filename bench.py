@@ -4,6 +4,7 @@
 architecture, arch_spec.py — the reference's model code is not in the mount).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--variant voxel|point] [--dtype f32|bf16]
+                    [--dump-outputs DIR]
 
 A "step" is one forward of the hot path over one resident batch of B pairs per GPU (inputs already in
 HBM).  N>1: one process per GPU, the batch is sharded (weak scaling: B pairs per rank), and each step
@@ -121,6 +122,27 @@ def self_launch(args):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"),
                MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS=os.environ.get("OMP_NUM_THREADS", "4"))
     return subprocess.run(cmd, env=env).returncode
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: each array as <outdir>/<name>.npy in float32 (the integer outputs are Chamfer indices < 2048: exact).
+    Above DUMP_LIMIT_BYTES in all, every array keeps the same fixed sample of its leading (batch) axis, drawn from seed 0, so
+    two builds run with the same arguments dump the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(4 * a.numel() for a in arrays.values())
+    for name, a in arrays.items():
+        a = a.float()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.shape[0] * DUMP_LIMIT_BYTES // total)
+            rows = torch.randperm(a.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a = a[rows]
+        np.save(os.path.join(outdir, name + ".npy"), a.numpy())
+        log(f"bench.py: wrote {os.path.join(outdir, name + '.npy')} {tuple(a.shape)}")
 
 
 def family_table(records, steps):
@@ -504,7 +526,13 @@ def main():
     ap.add_argument("--override", nargs="*", default=[], metavar="KIND.LAYER=INT",
                     help="tuning / diagnosis only: force descriptor fields of named layers for the whole run through "
                          "s3r.debug_overrides (tile.v2=2 ksplit.v4=2 algo.e6=1); the line is marked as not the plain configuration")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0: its predictions, the Chamfer "
+                         "tensors for --variant point, the all-gathered predictions at N>1) as DIR/<name>.npy, float32, "
+                         "64 MB at most (a fixed seeded sample of the batch beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("--steps must be at least 1")
     forced = parse_overrides(args.override)
 
     if args.same_device and args.backend == "nccl" and max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1:
@@ -596,8 +624,7 @@ def main():
             (graphed.left if graphed else left).copy_(host_l, non_blocking=True)
             (graphed.right if graphed else right).copy_(host_r, non_blocking=True)
         y = graphed() if graphed else model(left, right)
-        if gt_cloud is not None:
-            s3r.chamfer_distance(y, gt_cloud)
+        cd = s3r.chamfer_distance(y, gt_cloud) if gt_cloud is not None else None
         if dist_on:
             k = step_no[0] & 1
             step_no[0] += 1
@@ -605,7 +632,7 @@ def main():
                 pending[k].wait()                         # buffer k's previous collation (two steps ago) is done
             staged[k].copy_(y)                            # y is the graph's static output: the next replay overwrites it
             pending[k] = dist.all_gather_into_tensor(gathered[k], staged[k], async_op=True)   # RCCL over xGMI
-        return y
+        return y, cd
 
     def drain():
         if dist_on:
@@ -632,7 +659,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     drain()                                               # every step's collation has completed inside the timed region
     torch.cuda.synchronize()
     if dist_on:
@@ -642,6 +669,16 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+
+    outputs = None
+    if args.dump_outputs and rank == 0:                   # host copies now: the passes below overwrite the graph's output
+        y, cd = last
+        kind = "voxels" if args.variant == "voxel" else "points"
+        outputs = {kind: y.cpu()}
+        if cd is not None:
+            outputs.update(zip(("chamfer_dist1", "chamfer_dist2", "chamfer_idx1", "chamfer_idx2"), (x.cpu() for x in cd)))
+        if dist_on:
+            outputs["gathered_" + kind] = gathered[(step_no[0] - 1) & 1].cpu()
 
     records = []
     if profiling and graphed is None:                     # eager launches: the timed region's own kernel events
@@ -735,6 +772,8 @@ def main():
             out["secondary"] = sec
         if world == 1 and not args.no_cpu_baseline and not args.force_dist:
             out["cpu_baseline"] = cpu_baseline(32)
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
     if dist_on:
         dist.destroy_process_group()

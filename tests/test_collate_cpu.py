@@ -148,3 +148,27 @@ def test_bench_override_flag_parses_into_the_debug_context(s3r, monkeypatch):
     with s3r.debug_overrides(**kw):
         assert bench.kernel_env_overrides(s3r) == ["S3R_WINO", "algo.e6=1", "ksplit.v4=2", "tile.v2=2"]
     assert bench.kernel_env_overrides(s3r) == ["S3R_WINO"]
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_the_same_rows(tmp_path):
+    """`bench.py --dump-outputs DIR`: float32 .npy files (integer outputs converted exactly); above 64 MB in all, a fixed
+    seeded sample of the batch axis, the same rows in every array and on every run."""
+    import numpy as np
+    import bench
+    small = {"voxels": torch.rand(3, 4, 4, 4), "chamfer_idx1": torch.arange(6, dtype=torch.int32).reshape(3, 2)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for name, a in small.items():
+        got = np.load(tmp_path / "small" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a.float().numpy())
+    n = 40                                                             # 40 x 2 MB + 40 x 0.5 MB: 100 MB in all
+    big = {"a": torch.arange(n, dtype=torch.float32)[:, None].repeat(1, 1 << 19),
+           "b": torch.arange(n, dtype=torch.float32)[:, None].repeat(1, 1 << 17)}
+    bench.dump_outputs(str(tmp_path / "big1"), big)
+    bench.dump_outputs(str(tmp_path / "big2"), big)
+    a1, b1 = np.load(tmp_path / "big1" / "a.npy"), np.load(tmp_path / "big1" / "b.npy")
+    assert a1.nbytes + b1.nbytes <= bench.DUMP_LIMIT_BYTES and 0 < len(a1) < n
+    rows = a1[:, 0]
+    assert np.array_equal(rows, np.sort(rows)) and len(set(rows)) == len(rows) and (a1 == rows[:, None]).all()
+    assert np.array_equal(b1[:, 0], rows)                              # the same batch items in both arrays
+    assert np.array_equal(np.load(tmp_path / "big2" / "a.npy"), a1)
+    assert np.array_equal(np.load(tmp_path / "big2" / "b.npy"), b1)

@@ -733,17 +733,18 @@ def test_dataset_eval_with_exr_disparity(s3r, models, tmp_path):
 
 
 @pytest.mark.timeout(600)
-@pytest.mark.parametrize("launcher,world", [("self", 2), ("torchrun", 2), ("self", 8)])
+@pytest.mark.parametrize("launcher,world", [("self", 2), ("torchrun", 2), ("self", 4)])
 def test_bench_ranks_share_one_gpu(tmp_path, launcher, world):
     """bench.py's N>1 path (sharded batch, all-gather collation, barrier, max-over-ranks timing, rank-0 JSON) run
-    with `world` ranks sharing cuda:0 over gloo — the RCCL run itself needs a multi-GPU node — at two ranks and at the
-    real world size of BASELINE configs[4] (eight processes, eight arenas, eight host launch threads on one device).
+    with `world` ranks sharing cuda:0 over gloo — the RCCL run itself needs a multi-GPU node — at two ranks and at four
+    (four processes, four arenas, four host launch threads on one device; BASELINE configs[4]'s eight ranks are not run on
+    one device: with the test's own process that is more processes holding one GPU than a shared host allows).
     "self": plain `python bench.py --gpus N ...` as the driver invokes it (bench starts its own ranks as a child
     process); "torchrun": under an external launcher, as the contract's N>1 command line does."""
     import json, os, socket, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = [os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "4", "--backend",
-            "gloo", "--same-device", "--no-cpu-baseline"]
+            "gloo", "--same-device", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "dump")]
     if launcher == "self":
         cmd = [sys.executable] + args
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
@@ -762,6 +763,8 @@ def test_bench_ranks_share_one_gpu(tmp_path, launcher, world):
     assert d["n_gpus"] == world and d["steps"] == 3 and d["config"]["global_batch"] == 4 * world and d["scaling"] == "weak"
     assert d["n_ranks_seen"] == world and d["collective_backend"] == "gloo"
     assert d["value"] > 0 and "cpu_baseline" not in d and "secondary" not in d
+    own, gathered = np.load(tmp_path / "dump" / "voxels.npy"), np.load(tmp_path / "dump" / "gathered_voxels.npy")
+    assert own.shape == (4, 32, 32, 32) and gathered.shape == (4 * world, 32, 32, 32) and np.array_equal(gathered[:4], own)
 
 
 def test_bench_line_carries_roofline_border_excluded_and_secondaries(tmp_path):
@@ -795,6 +798,35 @@ def test_bench_line_carries_roofline_border_excluded_and_secondaries(tmp_path):
     assert sec["point_b32"]["value"] > 0 and "chamfer" in sec["point_b32"]["kernels"] and "linear" in sec["point_b32"]["kernels"]
     # three independent batches in flight on three streams: the same work per step, never the headline; not slower than 0.9 x it
     assert sec["in_flight3_b32"]["streams"] == 3 and sec["in_flight3_b32"]["value"] > 0.9 * d["value"]
+
+
+@pytest.mark.timeout(500)
+@pytest.mark.parametrize("variant", ["voxel", "point"])
+def test_bench_dump_outputs_are_what_the_timed_steps_returned(s3r, tmp_path, variant):
+    """`bench.py --steps K --dump-outputs DIR`: K timed steps in the line, and the files hold, bit for bit, what an eager forward
+    of the same seeded model on the same seeded inputs returns (plus the Chamfer tensors against the seeded cloud for point)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("S3R_")}
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--variant", variant, "--batch", "4", "--steps", "3",
+                          "--warmup", "1", "--no-secondary", "--no-cpu-baseline", "--no-profile", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=450, cwd=root, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    model = s3r.Stereo2Voxel() if variant == "voxel" else s3r.Stereo2Point()
+    s3r.seed_module(model, 0)
+    model.to(DEV)
+    left, right = s3r.synthetic_pairs(4, seed=1000)
+    y = model(left.to(DEV), right.to(DEV))
+    want = {("voxels" if variant == "voxel" else "points"): y}
+    if variant == "point":
+        cloud = torch.rand(4, s3r.arch_spec.N_POINTS, 3, generator=torch.Generator().manual_seed(77)).to(DEV)
+        want.update(zip(("chamfer_dist1", "chamfer_dist2", "chamfer_idx1", "chamfer_idx2"), s3r.chamfer_distance(y, cloud)))
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{k}.npy" for k in want)
+    for name, w in want.items():
+        got = np.load(tmp_path / f"{name}.npy")
+        assert got.dtype == np.float32 and torch.equal(torch.from_numpy(got), w.float().cpu()), name
 
 
 def test_maximum_sizes_chunking_and_limits(s3r, models):

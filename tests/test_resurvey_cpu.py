@@ -81,10 +81,11 @@ def test_resurvey_on_a_stand_in_tree(tmp_path):
     assert keys[0] == ["layer1.0.weight", [32, 3, 3, 3]]
 
 
-def test_resurvey_refuses_the_mount_as_it_is():
-    """Today's /root/reference (README.md + requirements.txt) has nothing to survey: the tool says so."""
-    if not os.path.isdir("/root/reference"):
-        return
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resurvey.py"), "--ref", "/root/reference"],
+def test_resurvey_refuses_the_mount_as_it_is(tmp_path):
+    """A tree laid out as the reference is mounted today (README.md + requirements.txt, no Python source) has nothing to
+    survey: the tool says so."""
+    (tmp_path / "README.md").write_text("# Stereo-3D-Reconstruction\n\nThe code lives on other branches.\n")
+    (tmp_path / "requirements.txt").write_text("easydict\nopencv-python\ntorch\n")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resurvey.py"), "--ref", str(tmp_path)],
                        capture_output=True, text=True, timeout=120, cwd=ROOT)
     assert r.returncode != 0 and "holds no Python source" in (r.stderr + r.stdout)
