@@ -126,7 +126,10 @@ typedef enum s3r_algo { S3R_ALGO_AUTO = 0, S3R_ALGO_DIRECT = 1, S3R_ALGO_WINOGRA
  * (B, C, n+2*halo, ...) tensor whose border is zero and whose interior is the logical (B, C, n, ...)
  * tensor.  `in_halo` / `out_halo` describe the buffers `x` / `y` of s3r_conv_forward.  A layer with
  * padding p (or a ConvTranspose) served by the MFMA kernel needs in_halo >= p (>= 1); kernels write
- * interiors only, so a buffer zeroed once keeps its halo.  s3r_chain_forward plans the halos of all
+ * interiors only, so a buffer zeroed once keeps its halo.  Two writers store whole padded rows instead (whole 128-byte lines:
+ * partial lines cost a read-modify-write) and so rewrite the halo rows / columns of the planes they write with +0.0, the value
+ * the halo holds: the two-axis Winograd Conv2d (its finish kernel) and the fp32 s3r_cost_volume_forward.  Neither ever writes
+ * anything but +0.0 there, nor a halo PLANE (depth) of a 3D output.  s3r_chain_forward plans the halos of all
  * intermediates itself and pads an unpadded chain input on the fly. */
 typedef struct s3r_conv_desc {
     int32_t op;        /* s3r_op */
@@ -201,7 +204,12 @@ int s3r_conv_forward(const s3r_conv_desc* d, const void* x, const void* packed_w
  * the next layer wants.  layers[0].desc.in_halo / layers[n-1].desc.out_halo describe x / y; the halos
  * of the intermediates are planned by the library (the descriptors' values are ignored for them).
  * `ws_fresh` != 0 makes the call zero the workspace first: pass 1 the first time a (chain, batch,
- * workspace) combination is used — or whenever anything else wrote to `ws` — and 0 afterwards. */
+ * workspace) combination is used — or whenever anything else wrote to `ws` — and 0 afterwards.
+ * A layer may read its input in another geometry than its producer wrote (a linear layer's features as a (C, n, n) map, or a
+ * conv's output as fewer channels over a larger edge): such an input carries no halo.  A consumer behind such a reshape stages its
+ * own padded copy where it has one (staged and unfolded layers, residue-class ConvTranspose); one that reads its zero padding from
+ * the producer's halo — a cin % 16 == 0 direct convolution with pad > 0, the Winograd forms, the tuned ConvTranspose3d k4 s2 p1 —
+ * is refused (S3R_ERR_INVALID).  Linear and head layers write no halo either: the same holds behind them. */
 int64_t s3r_chain_workspace_elems(const s3r_layer* layers, int n_layers);
 int s3r_chain_forward(const s3r_layer* layers, int n_layers, const void* x, void* y, float* ws, int64_t ws_elems,
                       int ws_fresh, void* stream);

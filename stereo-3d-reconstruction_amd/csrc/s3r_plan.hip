@@ -766,6 +766,14 @@ int resolve_launch(const s3r_conv_desc* d, s3r::ConvParams* p, Launch* L) {
     L->vec = code >> 4;
     if (L->cfg != 15 && L->cfg >= s3r::conv_num_tiles()) return fail(S3R_ERR_INVALID, "unknown tile configuration %d", L->cfg);
     if (L->cfg == 15) L->cfg = s3r::conv_pick_tile(*p);
+    // a forced tile wider than 256 gathers of the width the geometry allows has no kernel: refuse it here, not as a launch error
+    const int vmax = s3r::conv_pick_vec(*p);
+    const int vec = (L->vec == 1 || L->vec == 4) && L->vec <= vmax ? L->vec : vmax;
+    int bm, bn;
+    s3r::conv_tile_dims(L->cfg, &bm, &bn);
+    if (bn > 256 * vec)
+        return fail(S3R_ERR_INVALID, "tile configuration %d (%d positions) needs the 16-byte gather: rows of a multiple of 4 positions, "
+                    "stride 1", L->cfg, bn);
     return S3R_OK;
 }
 
@@ -792,7 +800,14 @@ int plan_chain(const s3r_layer* layers, int n, Plan* pl) {
     if (pl->pad_input) pl->d[0].in_halo = need0;
     for (int i = 0; i < n; ++i) {
         if (i > 0) pl->d[i].in_halo = pl->d[i - 1].out_halo;
-        if (i + 1 < n) pl->d[i].out_halo = want_halo(&pl->d[i + 1], pl->r[i + 1]);
+        if (i + 1 < n) {
+            // the wider halo a residue-class consumer reads in place only where the producer can carry it: a linear or head layer
+            // writes no halo, and a reshaped output has none in the consumer's geometry — such a consumer stages its own copy
+            const s3r_conv_desc& a = pl->d[i];
+            const s3r_conv_desc& b = pl->d[i + 1];
+            const bool carries = pl->r[i] != R_LINEAR && pl->r[i] != R_HEAD && out_size(&a) == b.in_size && a.cout == b.cin;
+            pl->d[i].out_halo = carries ? want_halo(&b, pl->r[i + 1]) : need_halo(&b, pl->r[i + 1]);
+        }
         if (i == 1 && pl->r[0] == R_STEM && pl->r[1] == R_MFMA && pl->d[1].dtype == S3R_F32 && pl->d[1].op == S3R_OP_CONV) {
             // a stem feeding the one-axis Winograd kernel writes that kernel's planes itself (the same bits: the stem's values
             // through wino_input_kernel's transform): no plain activation, no transform launch
