@@ -19,6 +19,10 @@
  *   s3r_voxel_iou                           the IoU metric of `runner.py --test`        (README.md:88-92)
  *   s3r_disparity_wta, s3r_disparity_epe    predicted left / right disparity and its end-point error
  *                                           against the disp_%02d_{l,r}.exr ground truth (README.md:75-76)
+ *   s3r_disparity_soft                      the same prediction as a sub-pixel soft-argmin, upsampled to the
+ *                                           ground truth's render resolution, with a confidence map   (README.md:75-76)
+ *   s3r_disparity_metrics                   the end-point error and bad-pixel rates (>1 px, >3 px, KITTI D1) of a
+ *                                           stereo evaluation against those maps        (README.md:75-76)
  *
  * Conventions
  *   - every tensor is fp32, contiguous, NCHW / NCDHW, resident in device memory owned by the caller;
@@ -44,7 +48,9 @@ extern "C" {
 
 /* ABI 8 (r05) over ABI 7: s3r_conv_desc grew `dilation`, `out_pad`, `act_param` and three activations — the parameter-general
  * fp32 layers; `tile` = 6 under S3R_ALGO_WINOGRAD names the three-axis form of a transposed convolution (AUTO takes it from edge
- * 16 up: other bits than ABI 7 for such a layer); s3r_profile_detail and record family 10 (aux passes). */
+ * 16 up: other bits than ABI 7 for such a layer); s3r_profile_detail and record family 10 (aux passes).
+ * s3r_disparity_soft and s3r_disparity_metrics were added later as new entry points only (no struct or existing signature changed):
+ * the version stays 8. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -289,6 +295,29 @@ int s3r_disparity_wta(const float* feat_l, const float* feat_r, float* disp_l, f
  * pixel count; epe = 0 where no pixel is valid */
 int s3r_disparity_epe(const float* pred, const float* gt, float* epe, int32_t* count, int batch, int64_t pixels,
                       void* stream);
+
+/* Sub-pixel disparity read-out (a stand-in like the WTA: no learned head).  Per sample, direction and feature pixel (h, w):
+ *   c(d) = the WTA's costs above, bit for bit (fp32, c ascending, |a-b| then add), d in [0, n-1], n = min(max_disp-1, w)+1 (left)
+ *          or min(max_disp-1, W-1-w)+1 (right);
+ *   e_d  = expf((min_d c(d) - c(d)) / temperature) (a weight that would be subnormal is 0), Z = sum e_d, S = sum d e_d, d ascending;
+ *   disp = S / Z (feature pixels), conf = 1 / Z (the probability of the best disparity); max_disp = 1 gives exactly 0 and 1.
+ * Output (batch, out_height, out_width) per map: at the feature size the values as they are, otherwise upsampled bilinearly with
+ * torch's align_corners=False convention (src = (dst + 0.5) in / out - 0.5, clamped at 0, upper neighbour clamped at in - 1);
+ * disp is then multiplied by disp_scale, conf is not.  Both directions, all samples, one kernel launch.
+ * feat_dtype S3R_F32: feat_* fp32 (B,C,H,W); S3R_BF16: bf16 channels-last (B,H,W,C) as the bf16 encoder emits it, channels % 8 == 0,
+ * 16-byte aligned — bf16 widens to fp32 exactly, so the result equals the S3R_F32 call on s3r_channels_last_to_f32's output bit for
+ * bit.  Any of disp_l, disp_r, conf_l, conf_r may be NULL: it is not written.  LDS: 4 (2 C W + 2 W min(max_disp, W) + 12 W) bytes
+ * must fit 64 KiB.  temperature finite and > 0; batch == 0 launches nothing.  Profiler: family 9, tag 2. */
+int s3r_disparity_soft(const void* feat_l, const void* feat_r, int feat_dtype, float* disp_l, float* disp_r, float* conf_l,
+                       float* conf_r, int batch, int channels, int height, int width, int max_disp, float temperature,
+                       int out_height, int out_width, float disp_scale, void* stream);
+
+/* Stereo metrics per sample over `pixels` elements; valid pixels as s3r_disparity_epe (ground truth finite and >= 0).
+ * epe[b] equals s3r_disparity_epe's bit for bit (same fp64 order); counts[b][0..3] (int32, (B,4)) = valid pixels, |err| > 1,
+ * |err| > 3, D1 (|err| > 3 and |err| > 0.05 gt, in fp64), all strict: integers, so rates pool exactly over samples and ranks.
+ * batch == 0 launches nothing.  Profiler: family 9, tag 3. */
+int s3r_disparity_metrics(const float* pred, const float* gt, float* epe, int32_t* counts, int batch, int64_t pixels,
+                          void* stream);
 
 /* Kernel-level profiler: when enabled, every kernel the library launches is bracketed by HIP events
  * on the launch stream.  s3r_profile_read synchronises those events and returns, per launch, the

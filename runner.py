@@ -40,6 +40,12 @@ def main():
                     help="StereoShapeNet root (ShapeNetStereoRendering/ + ShapeNetVox32/, README.md:73-77)")
     ap.add_argument("--disparity", action="store_true",
                     help="with --dataset-root: also read disp_%%02d_{l,r}.exr and report the disparity end-point error")
+    ap.add_argument("--disparity-readout", default="wta", choices=["wta", "soft"],
+                    help="disparity read-out the disparity metrics use: wta (default: integer, at feature resolution, against "
+                         "28x28 ground truth) or soft (sub-pixel soft-argmin, compared at the ground truth's resolution: the "
+                         "224x224 EXR maps as they are, or (N,224,224) / (N,28,28) .npz maps); soft adds the bad-pixel rates")
+    ap.add_argument("--disparity-temperature", type=float, default=None,
+                    help="temperature of the soft read-out (default: s3r.DISPARITY_TEMPERATURE)")
     ap.add_argument("--variant", default="voxel", choices=["voxel", "point"],
                     help="voxel: Stereo2Voxel + IoU (default); point: Stereo2Point + Chamfer distance (.npz key `points`, "
                          "(N,M,3); synthetic clouds otherwise)")
@@ -63,6 +69,10 @@ def main():
                     help="evaluate on N GPUs of this node: the eval list is sharded over one process per GPU (RCCL "
                          "all-gather of the per-sample metrics); runner.py starts the ranks itself")
     args = ap.parse_args()
+    if args.disparity_temperature is not None and args.disparity_readout != "soft":
+        sys.exit("--disparity-temperature needs --disparity-readout soft")
+    if args.disparity_temperature is not None and not (0 < args.disparity_temperature < float("inf")):
+        sys.exit("--disparity-temperature must be finite and > 0")
     if args.same_device and args.backend == "nccl" and max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1:
         sys.exit("--same-device puts every rank on cuda:0, which RCCL refuses (one communicator rank per device): "
                  "use --backend gloo with it")
@@ -139,6 +149,8 @@ def main():
             s3r.evaluate.test_point_net(model, ws[0], ws[1], torch.rand(nw, 2048, 3) - 0.5, batch=2, device=dev)
         else:
             s3r.evaluate.test_net(model, ws[0], ws[1], ws[2], batch=2, device=dev)
+            if args.disparity_readout == "soft":                # (the soft read-out's first launch as well)
+                model.disparity(ws[0][:2].to(dev), ws[1][:2].to(dev), readout="soft", full_resolution=True)
         zeros = torch.zeros(wb, 3, 224, 224, dtype=ws[0].dtype, device=dev)
         model(zeros, zeros)                                     # back to the eval batch's arena layout
         del zeros
@@ -201,10 +213,11 @@ def main():
     disp = None
     if args.dataset_root:
         ds = s3r.data.StereoShapeNet(args.dataset_root, with_disparity=args.disparity, render_dtype=rdt)
-        res = timed(s3r.evaluate.test_dataset, model, ds, batch=args.batch, device=dev, workers=args.workers)
+        res = timed(s3r.evaluate.test_dataset, model, ds, batch=args.batch, device=dev, workers=args.workers,
+                    disparity_readout=args.disparity_readout, disparity_temperature=args.disparity_temperature)
         left = None
         if args.disparity:
-            disp = {"epe_left": res["epe_left"], "epe_right": res["epe_right"]}
+            disp = res
     elif args.data:
         z = np.load(args.data)
         left, right, gt = renders(z["left"]), renders(z["right"]), torch.from_numpy(z["volume"]).float()
@@ -213,9 +226,11 @@ def main():
     if left is not None:
         res = timed(s3r.evaluate.test_net, model, left, right, gt, batch=args.batch, device=dev)
         if args.data and "disp_left" in z.files and "disp_right" in z.files:
-            # (N,28,28) ground-truth disparity at feature resolution, render pixels; inf / negative = invalid
+            # ground-truth disparity in render pixels, (N,28,28) at feature resolution (soft: or (N,224,224)); inf / negative =
+            # invalid
             disp = s3r.evaluate.test_disparity(model, left, right, torch.from_numpy(z["disp_left"]).float(),
-                                               torch.from_numpy(z["disp_right"]).float(), batch=args.batch, device=dev)
+                                               torch.from_numpy(z["disp_right"]).float(), batch=args.batch, device=dev,
+                                               readout=args.disparity_readout, temperature=args.disparity_temperature)
     info = dist_info()
     if rank == 0:
         out = {"samples": res["samples"], "n_gpus": world, "thresholds": res["thresholds"],
@@ -229,6 +244,10 @@ def main():
                                    for k, v in res["per_taxonomy"].items()}
         if disp is not None:
             out.update({"disparity_epe_left_px": round(disp["epe_left"], 4), "disparity_epe_right_px": round(disp["epe_right"], 4)})
+            if args.disparity_readout == "soft":
+                out["disparity_readout"] = "soft"
+                out.update({f"disparity_{k}_{side}_pct": round(disp[f"{k}_{side}"], 4)
+                            for k in ("bad1", "bad3", "d1") for side in ("left", "right")})
         out.update(info)
         print(json.dumps(out))
     if dist_on:

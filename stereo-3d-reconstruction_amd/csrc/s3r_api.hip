@@ -3,6 +3,7 @@
 // heads).  Planning (geometry, kernel policy, sizes, the arena) lives in s3r_plan.hip, the profiler in s3r_prof.hip.  Host code only.
 #include "s3r_host.h"
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -873,6 +874,56 @@ int s3r_disparity_epe(const float* pred, const float* gt, float* epe, int32_t* c
     ProfScope ps(s, F_DISP, 1, 0.0, 8.0 * batch * (double)pixels);
     hipError_t e = s3r::launch_disparity_epe(pred, gt, epe, count, batch, pixels, s);
     if (e != hipSuccess) return hip_fail(e, "epe launch");
+    return S3R_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- sub-pixel read-out and stereo metrics (s3r_disparity.hip)
+extern "C" {
+
+int s3r_disparity_soft(const void* feat_l, const void* feat_r, int feat_dtype, float* disp_l, float* disp_r, float* conf_l,
+                       float* conf_r, int batch, int channels, int height, int width, int max_disp, float temperature,
+                       int out_height, int out_width, float disp_scale, void* stream) {
+    if (!(temperature > 0.f) || !std::isfinite(temperature))
+        return fail(S3R_ERR_INVALID, "soft read-out temperature must be finite and > 0 (got %g)", (double)temperature);
+    if (batch < 0 || channels <= 0 || height <= 0 || width <= 0 || max_disp <= 0 || out_height <= 0 || out_width <= 0)
+        return fail(S3R_ERR_INVALID, "soft read-out dims must be positive (batch >= 0)");
+    if (feat_dtype != S3R_F32 && feat_dtype != S3R_BF16) return fail(S3R_ERR_INVALID, "unknown feature dtype %d", feat_dtype);
+    const bool bf16 = feat_dtype == S3R_BF16;
+    if (bf16 && channels % 8 != 0) return fail(S3R_ERR_INVALID, "bf16 channels-last features need channels %% 8 == 0");
+    if (s3r::disparity_soft_lds_bytes(channels, max_disp, width) > 64 * 1024)
+        return fail(S3R_ERR_INVALID, "soft read-out: 4*(2*C*W + 2*W*min(max_disp, W) + 12*W) bytes must fit 64 KiB of LDS");
+    const int64_t feat = (int64_t)batch * channels * height * width;
+    const int64_t out = (int64_t)batch * out_height * out_width;
+    if (feat >= kMaxElems || out >= kMaxElems) return fail(S3R_ERR_INVALID, "tensor of 2^31 elements or more: split the batch");
+    if ((int64_t)batch * out_height >= (1 << 24))      // at most one workgroup of 256 per output row: < 2^32 work-items
+        return fail(S3R_ERR_INVALID, "batch x out_height must stay below 2^24: split the batch");
+    if (batch == 0) return S3R_OK;
+    if (!feat_l || !feat_r) return fail(S3R_ERR_INVALID, "null feature pointer");
+    if (bf16 && (((uintptr_t)feat_l | (uintptr_t)feat_r) & 15))
+        return fail(S3R_ERR_INVALID, "bf16 features must start 16-byte aligned (16-byte loads)");
+    hipStream_t s = (hipStream_t)stream;
+    const int maps = !!disp_l + !!disp_r + !!conf_l + !!conf_r;
+    ProfScope ps(s, F_DISP, 2, 0.0, (bf16 ? 2.0 : 4.0) * 2.0 * (double)feat + 4.0 * maps * (double)out);
+    hipError_t e = s3r::launch_disparity_soft(feat_l, feat_r, bf16, disp_l, disp_r, conf_l, conf_r, batch, channels, max_disp,
+                                              height, width, temperature, out_height, out_width, disp_scale, s);
+    if (e != hipSuccess) return hip_fail(e, "soft disparity read-out launch");
+    return S3R_OK;
+}
+
+int s3r_disparity_metrics(const float* pred, const float* gt, float* epe, int32_t* counts, int batch, int64_t pixels,
+                          void* stream) {
+    if (batch < 0 || pixels < 0) return fail(S3R_ERR_INVALID, "metrics dims must be >= 0 (batch %d, pixels %lld)", batch,
+                                             (long long)pixels);
+    if (batch > 65535) return fail(S3R_ERR_INVALID, "batch > 65535: split the call");
+    if (pixels >= kMaxElems || (int64_t)batch * pixels >= kMaxElems) return fail(S3R_ERR_INVALID, "tensor of 2^31 elements or more: split the batch");
+    if (batch == 0) return S3R_OK;
+    if (!pred || !gt || !epe || !counts) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(s, F_DISP, 3, 0.0, 8.0 * batch * (double)pixels + 20.0 * batch);
+    hipError_t e = s3r::launch_disparity_metrics(pred, gt, epe, counts, batch, pixels, s);
+    if (e != hipSuccess) return hip_fail(e, "disparity metrics launch");
     return S3R_OK;
 }
 

@@ -287,6 +287,13 @@ hipError_t launch_disparity_wta(const float* fl, const float* fr, float* dl, flo
                                 hipStream_t s);
 hipError_t launch_disparity_epe(const float* pred, const float* gt, float* epe, int* count, int B, int64_t S,
                                 hipStream_t s);
+// s3r_disparity.hip: the soft read-out (fp32 NCHW features, or bf16 channels-last when bf16 != 0; NULL outputs are not written)
+// and the metrics; disparity_soft_lds_bytes is the workgroup's LDS, which the API checks against 64 KiB
+size_t disparity_soft_lds_bytes(int C, int D, int W);
+hipError_t launch_disparity_soft(const void* fl, const void* fr, int bf16, float* dl, float* dr, float* cl, float* cr, int B,
+                                 int C, int D, int H, int W, float tau, int OH, int OW, float disp_scale, hipStream_t s);
+hipError_t launch_disparity_metrics(const float* pred, const float* gt, float* epe, int* counts, int B, int64_t S,
+                                    hipStream_t s);
 
 #if defined(__HIPCC__)
 // Winograd F(4, 3) input transform along one axis (s3r_conv_wino.hip): the six class values of six consecutive padded rows.

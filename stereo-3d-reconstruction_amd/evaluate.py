@@ -12,8 +12,9 @@ from typing import Dict, Iterable, Optional, Sequence, Tuple
 
 import torch
 
+from . import arch_spec as spec
 from . import collate
-from .modules import chamfer_distance, disparity_epe, voxel_iou
+from .modules import READOUTS, chamfer_distance, disparity_metrics, voxel_iou
 
 THRESHOLDS = (0.2, 0.3, 0.4, 0.5)
 
@@ -88,13 +89,51 @@ def synthetic_eval_set(n: int, seed: int = 0, render_dtype: str = "float32") -> 
     return left, right, gt
 
 
+# per-sample disparity rows (float64: integer counts stay exact): epe_l, n_l, epe_r, n_r, then >1 px, >3 px, D1 counts left, right
+_DISP_COLS = 10
+
+
+def _disparity_rows(model, l, r, gl, gr, readout: str, temperature) -> torch.Tensor:
+    """the model's (left, right) read-out against ground truth gl / gr of one device batch -> (n, _DISP_COLS) float64 rows.
+    readout="soft" reads out at the ground truth's resolution: (n,224,224) render-resolution maps or (n,28,28) feature-resolution
+    ones; "wta" predicts at feature resolution only."""
+    if readout not in READOUTS:
+        raise ValueError(f"readout must be one of {READOUTS}, got {readout!r}")
+    if readout == "soft":
+        full = tuple(gl.shape[-2:]) == (spec.IMG_HW, spec.IMG_HW)
+        if not full and tuple(gl.shape[-2:]) != (spec.FEAT_HW, spec.FEAT_HW):
+            raise ValueError(f"soft read-out: ground truth must be (N,{spec.IMG_HW},{spec.IMG_HW}) or (N,{spec.FEAT_HW},{spec.FEAT_HW}), "
+                             f"got {tuple(gl.shape)}")
+        dl, dr = model.disparity(l, r, readout="soft", temperature=temperature, full_resolution=full)
+    else:
+        dl, dr = model.disparity(l, r)
+    el, cl = disparity_metrics(dl, gl)
+    er, cr = disparity_metrics(dr, gr)
+    cl, cr = cl.double(), cr.double()
+    return torch.cat([torch.stack([el.double(), cl[:, 0], er.double(), cr[:, 0]], 1), cl[:, 1:], cr[:, 1:]], 1)
+
+
+def _disparity_pooled(rows: torch.Tensor) -> Dict[str, object]:
+    """EPE pooled over every valid pixel of the list and the bad-pixel rates (percent of valid pixels) from the integer counts"""
+    out: Dict[str, object] = {}
+    for side, e, n, c0 in (("left", 0, 1, 4), ("right", 2, 3, 7)):
+        nv = rows[:, n].sum().item()
+        out[f"epe_{side}"] = (rows[:, e] * rows[:, n]).sum().item() / nv if nv else float("nan")
+        out[f"valid_{side}"] = int(nv)
+        for k, name in enumerate(("bad1", "bad3", "d1")):
+            out[f"{name}_{side}"] = 100.0 * rows[:, c0 + k].sum().item() / nv if nv else float("nan")
+    return out
+
+
 @torch.no_grad()
 def test_dataset(model, ds, batch: int = 32, thresholds: Sequence[float] = THRESHOLDS, device="cuda", group=None,
-                 workers: int = 0) -> Dict[str, object]:
+                 workers: int = 0, disparity_readout: str = "wta", disparity_temperature: Optional[float] = None) -> Dict[str, object]:
     """test_net over a data.StereoShapeNet: each rank decodes and evaluates only its shard_bounds slice of the item
     list, host batches cross PCIe on a copy stream while the previous batch runs (graph.PrefetchingLoader), and the
     per-sample IoUs are all-gathered in list order.  A dataset built with_disparity=True also yields the end-point error
-    of the model's disparity read-out against the EXR ground truth, pooled over valid pixels (see test_disparity)."""
+    and bad-pixel rates of the model's disparity read-out against the EXR ground truth, pooled over valid pixels (see
+    test_disparity): disparity_readout="wta" against the maps block-averaged to 28x28 (downsample_disparity), "soft" against
+    the 224x224 maps as they are."""
     import torch.distributed as dist
     from . import data as _data
     from .graph import PrefetchingLoader
@@ -105,7 +144,9 @@ def test_dataset(model, ds, batch: int = 32, thresholds: Sequence[float] = THRES
     b0, e0 = collate.shard_bounds(total, world, rank)
     ious = torch.empty((e0 - b0, len(thresholds)), dtype=torch.float32, device=device)
     with_disp = bool(getattr(ds, "with_disparity", False))
-    rows = torch.zeros((e0 - b0, 4), dtype=torch.float64, device=device)          # epe_l, n_l, epe_r, n_r
+    if with_disp and disparity_readout not in READOUTS:
+        raise ValueError(f"disparity_readout must be one of {READOUTS}, got {disparity_readout!r}")
+    rows = torch.zeros((e0 - b0, _DISP_COLS), dtype=torch.float64, device=device)
     host = _data.batches(ds, batch, range(b0, e0), workers)
     done = 0
     for item in PrefetchingLoader(host, device):
@@ -114,10 +155,10 @@ def test_dataset(model, ds, batch: int = 32, thresholds: Sequence[float] = THRES
         for j, t in enumerate(thresholds):
             ious[done:done + l.shape[0], j] = voxel_iou(pred, g, t)
         if with_disp:
-            dl, dr = model.disparity(l, r)
-            el, nl = disparity_epe(dl, _data.downsample_disparity(item[3], dl.shape[-1]))
-            er, nr = disparity_epe(dr, _data.downsample_disparity(item[4], dr.shape[-1]))
-            rows[done:done + l.shape[0]] = torch.stack([el.double(), nl.double(), er.double(), nr.double()], 1)
+            gl, gr = item[3], item[4]
+            if disparity_readout == "wta":
+                gl, gr = _data.downsample_disparity(gl, spec.FEAT_HW), _data.downsample_disparity(gr, spec.FEAT_HW)
+            rows[done:done + l.shape[0]] = _disparity_rows(model, l, r, gl, gr, disparity_readout, disparity_temperature)
         done += l.shape[0]
     if dist_on:
         ious = collate.all_gather_ragged(ious, total, group)
@@ -133,10 +174,9 @@ def test_dataset(model, ds, batch: int = 32, thresholds: Sequence[float] = THRES
         per_tax[tax] = {"samples": len(idx), "mean_iou": cpu[idx].mean(0).tolist()}
     out["per_taxonomy"] = per_tax
     if with_disp:
-        rows = rows.cpu()
-        nl, nr = rows[:, 1].sum().item(), rows[:, 3].sum().item()
-        out["epe_left"] = (rows[:, 0] * rows[:, 1]).sum().item() / nl if nl else float("nan")
-        out["epe_right"] = (rows[:, 2] * rows[:, 3]).sum().item() / nr if nr else float("nan")
+        pooled = _disparity_pooled(rows.cpu())
+        out.update({k: v for k, v in pooled.items() if not k.startswith("valid_")})
+        out["disparity_readout"] = disparity_readout
     return out
 
 
@@ -166,11 +206,15 @@ def test_point_net(model, left: torch.Tensor, right: torch.Tensor, gt_clouds: to
 
 @torch.no_grad()
 def test_disparity(model, left: torch.Tensor, right: torch.Tensor, disp_l_gt: torch.Tensor, disp_r_gt: torch.Tensor,
-                   batch: int = 32, device="cuda", group=None) -> Dict[str, object]:
-    """End-point error of the model's predicted left / right disparity (Stereo2Voxel.disparity, render pixels) against
-    (N,28,28) ground-truth maps at feature resolution in render pixels (the dataset's
-    disp_%02d_{l,r}.exr, /root/reference/README.md:75-76, downsampled by the caller; invalid pixels: inf / negative).
-    EPE is pooled over all valid pixels of the list: per-sample (sum, count) pairs are reduced on the device and, with
+                   batch: int = 32, device="cuda", group=None, readout: str = "wta",
+                   temperature: Optional[float] = None) -> Dict[str, object]:
+    """End-point error and bad-pixel rates of the model's predicted left / right disparity (Stereo2Voxel.disparity, render
+    pixels) against ground-truth maps in render pixels (the dataset's disp_%02d_{l,r}.exr,
+    /root/reference/README.md:75-76; invalid pixels: inf / negative).  readout="wta": (N,28,28) ground truth at feature
+    resolution (downsampled by the caller).  readout="soft": the sub-pixel read-out at `temperature` (default: the model's
+    disparity_temperature) compared at the ground truth's own resolution, (N,224,224) render resolution or (N,28,28).
+    EPE is pooled over all valid pixels of the list, and bad1 / bad3 / d1 (percent of valid pixels with |err| > 1 px, > 3 px,
+    > 3 px and > 5 % of the ground truth) from integer counts: per-sample rows are reduced on the device and, with
     torch.distributed initialised, all-gathered (rank order = list order)."""
     import torch.distributed as dist
     dist_on = dist.is_available() and dist.is_initialized()
@@ -178,22 +222,21 @@ def test_disparity(model, left: torch.Tensor, right: torch.Tensor, disp_l_gt: to
     rank = dist.get_rank(group) if dist_on else 0
     total = left.shape[0]
     b0, e0 = collate.shard_bounds(total, world, rank)
-    rows = torch.zeros((e0 - b0, 4), dtype=torch.float64, device=device)        # epe_l, n_l, epe_r, n_r
+    if readout not in READOUTS:
+        raise ValueError(f"readout must be one of {READOUTS}, got {readout!r}")
+    rows = torch.zeros((e0 - b0, _DISP_COLS), dtype=torch.float64, device=device)
     done = 0
     for l, r, gl, gr in _device_batches((left, right, disp_l_gt, disp_r_gt), b0, e0, batch, device):
-        dl, dr = model.disparity(l, r)
-        el, nl = disparity_epe(dl, gl)
-        er, nr = disparity_epe(dr, gr)
-        rows[done:done + l.shape[0]] = torch.stack([el.double(), nl.double(), er.double(), nr.double()], 1)
+        rows[done:done + l.shape[0]] = _disparity_rows(model, l, r, gl, gr, readout, temperature)
         done += l.shape[0]
     if dist_on:
         rows = collate.all_gather_ragged(rows, total, group)
     rows = rows.cpu()
-    nl, nr = rows[:, 1].sum().item(), rows[:, 3].sum().item()
-    epe_l = (rows[:, 0] * rows[:, 1]).sum().item() / nl if nl else float("nan")
-    epe_r = (rows[:, 2] * rows[:, 3]).sum().item() / nr if nr else float("nan")
-    return {"samples": total, "epe_left": epe_l, "epe_right": epe_r, "valid_left": int(nl), "valid_right": int(nr),
-            "per_sample": rows}
+    out = {"samples": total, "readout": readout}
+    out.update(_disparity_pooled(rows))
+    out["per_sample"] = rows[:, :4]                                        # epe_l, n_l, epe_r, n_r
+    out["counts"] = torch.stack([rows[:, [1, 4, 5, 6]], rows[:, [3, 7, 8, 9]]], 1).long()   # (N, left/right, 4)
+    return out
 
 
 @torch.no_grad()

@@ -670,14 +670,35 @@ class PointHead(_HipChain):
         return self._run(x.view(x.shape[0], spec.LATENT_C * 64)).view(x.shape[0], spec.N_POINTS, 3)   # (B may be 0)
 
 
+# Default temperature of the soft read-out (`disparity_soft`, `disparity(readout="soft")`), in units of the matching cost (a sum of
+# C = 32 absolute feature differences).  BUILD-SPECIFIED: no learned disparity head exists to fix it.
+DISPARITY_TEMPERATURE = 1.0
+
+READOUTS = ("wta", "soft")
+
+
 class _DisparityMixin:
     """`disparity()` for the networks that hold an `encoder` and a `cost_volume`."""
 
+    disparity_temperature = DISPARITY_TEMPERATURE      # what disparity(readout="soft") uses when temperature is None
+
     @torch.no_grad()
-    def disparity(self, left: torch.Tensor, right: torch.Tensor, in_pixels: bool = True):
-        """Predicted (left, right) disparity maps, (B,28,28) each: the winner-take-all read-out of the cost volume's
-        shift-and-diff costs on this model's encoder features (`disparity_wta`).  in_pixels scales feature-resolution
-        disparities to 224x224 render pixels (x8), the unit of the dataset's EXR ground truth."""
+    def disparity(self, left: torch.Tensor, right: torch.Tensor, in_pixels: bool = True, readout: str = "wta",
+                  temperature: Optional[float] = None, full_resolution: bool = False, confidence: bool = False):
+        """Predicted (left, right) disparity maps from this model's encoder features.
+
+        readout="wta" (default): the winner-take-all read-out of the cost volume's shift-and-diff costs (`disparity_wta`), (B,28,28)
+        each, integer feature pixels.  readout="soft": the sub-pixel soft-argmin over the same costs (`disparity_soft`) at
+        `temperature` (default: the `disparity_temperature` attribute), (B,28,28), or (B,224,224) upsampled bilinearly when
+        full_resolution; confidence=True also returns the two confidence maps (dl, dr, cl, cr).  Both are stand-in read-outs, not
+        a learned head.  in_pixels scales disparities to 224x224 render pixels (x8), the unit of the dataset's EXR ground truth."""
+        if readout not in READOUTS:
+            raise ValueError(f"readout must be one of {READOUTS}, got {readout!r}")
+        if readout == "wta" and (full_resolution or confidence or temperature is not None):
+            raise ValueError("full_resolution / confidence / temperature need readout='soft' (the WTA read-out is integer, "
+                             "at feature resolution)")
+        if readout == "soft":
+            return self._disparity_soft(left, right, in_pixels, temperature, full_resolution, confidence)
         left = _check_render(left, "left")
         right = _check_render(right, "right")
         if left.shape[0] != right.shape[0]:
@@ -695,6 +716,22 @@ class _DisparityMixin:
         dr = drs[0] if len(drs) == 1 else torch.cat(drs, 0)
         scale = float(spec.IMG_HW // spec.FEAT_HW) if in_pixels else 1.0
         return dl * scale, dr * scale
+
+    def _disparity_soft(self, left, right, in_pixels, temperature, full_resolution, confidence):
+        tau = float(self.disparity_temperature if temperature is None else temperature)
+        left = _check_render(left, "left")
+        right = _check_render(right, "right")
+        if left.shape[0] != right.shape[0]:
+            raise RuntimeError("left and right batch sizes differ")
+        scale = float(spec.IMG_HW // spec.FEAT_HW) if in_pixels else 1.0
+        size = (spec.IMG_HW, spec.IMG_HW) if full_resolution else None
+        parts = []
+        for s in range(0, max(left.shape[0], 1), MAX_CHUNK):
+            l, r = left[s:s + MAX_CHUNK], right[s:s + MAX_CHUNK]
+            b = l.shape[0]
+            feats = self.encoder.forward_pair(l, r)            # fp32 NCHW, or the bf16 channels-last features as they are
+            parts.append(disparity_soft(feats[:b], feats[b:], self.cost_volume.max_disp, tau, size, scale, confidence))
+        return tuple(p[0] if len(parts) == 1 else torch.cat(p, 0) for p in zip(*parts))
 
 
 class Stereo2Voxel(_DisparityMixin, nn.Module):
@@ -856,6 +893,55 @@ def disparity_wta(feat_l: torch.Tensor, feat_r: torch.Tensor, max_disp: int = sp
         _lib.check(_lib.load().s3r_disparity_wta(feat_l.data_ptr(), feat_r.data_ptr(), dl.data_ptr(), dr.data_ptr(), B,
                                                  Cc, H, W, int(max_disp), _stream_ptr(feat_l.device)), "disparity_wta")
     return dl, dr
+
+
+@torch.no_grad()
+def disparity_soft(feat_l: torch.Tensor, feat_r: torch.Tensor, max_disp: int = spec.MAX_DISP, temperature: float = 1.0,
+                   out_size: Optional[Sequence[int]] = None, scale: float = 1.0, confidence: bool = False):
+    """Sub-pixel disparity read-out (`s3r_disparity_soft`; a stand-in like `disparity_wta`, not a learned head): per pixel the
+    soft-argmin sum_d d p_d, p_d = softmax_d(-c(d) / temperature), over the SAME shift-and-diff costs c(d) the WTA takes the argmin
+    of, and the confidence p_best = 1 / sum_d exp((min c - c(d)) / temperature).  Features: fp32 (B,C,H,W), or the bf16 encoder's
+    logical (B,C,H,W) channels-last tensors as they are (no conversion pass; same bits as the fp32 call on `channels_last_to_f32`).
+    out_size=None: (B,H,W) maps; else (B,*out_size), upsampled bilinearly (torch's align_corners=False).  Disparities are
+    multiplied by `scale` (8: render pixels).  Returns (dl, dr), or (dl, dr, cl, cr) with confidence=True.  One kernel launch; torch
+    only allocates."""
+    if feat_l.dim() != 4 or feat_l.shape != feat_r.shape:
+        raise RuntimeError("feat_l / feat_r must be two (B,C,H,W) tensors of one shape")
+    if feat_l.dtype != feat_r.dtype or feat_l.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"features must both be float32 (NCHW) or bfloat16 (channels-last), got {feat_l.dtype} / {feat_r.dtype}")
+    bf16 = feat_l.dtype == torch.bfloat16
+    chk = _check_input_cl if bf16 else _check_input
+    pl, pr = chk(feat_l, "feat_l", feat_l.shape[1:], feat_l.dtype), chk(feat_r, "feat_r", feat_r.shape[1:], feat_r.dtype)
+    if bf16:                        # the kernel reads bf16 rows in 16-byte pieces: a view at an odd storage offset is copied once
+        pl, pr = (p if p.data_ptr() % 16 == 0 else p.clone() for p in (pl, pr))
+    B, Cc, H, W = feat_l.shape
+    OH, OW = (H, W) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    dev = feat_l.device
+    outs = [torch.empty((B, OH, OW), dtype=torch.float32, device=dev) for _ in range(4 if confidence else 2)]
+    if B:
+        ptr = [o.data_ptr() for o in outs] + [None] * (4 - len(outs))
+        _lib.check(_lib.load().s3r_disparity_soft(pl.data_ptr(), pr.data_ptr(), _lib.DTYPE["bf16" if bf16 else "fp32"], *ptr, B,
+                                                  Cc, H, W, int(max_disp), float(temperature), OH, OW, float(scale),
+                                                  _stream_ptr(dev)), "disparity_soft")
+    return tuple(outs)
+
+
+@torch.no_grad()
+def disparity_metrics(pred: torch.Tensor, gt: torch.Tensor):
+    """Stereo metrics per sample (`s3r_disparity_metrics`) over the pixels whose ground truth is valid (finite, >= 0):
+    (B,...) x2 fp32 -> (epe (B,) fp32, equal bit for bit to `disparity_epe`; counts (B,4) int32 = valid pixels, |err| > 1,
+    |err| > 3, D1 = |err| > 3 and |err| > 0.05 gt).  Integer counts: rates pool exactly over samples and ranks."""
+    if pred.shape != gt.shape:
+        raise RuntimeError("pred and gt shapes differ")
+    pred = _check_input(pred, "pred", pred.shape[1:])
+    gt = _check_input(gt, "gt", gt.shape[1:])
+    B = pred.shape[0]
+    epe = torch.empty((B,), dtype=torch.float32, device=pred.device)
+    counts = torch.empty((B, 4), dtype=torch.int32, device=pred.device)
+    if B:
+        _lib.check(_lib.load().s3r_disparity_metrics(pred.data_ptr(), gt.data_ptr(), epe.data_ptr(), counts.data_ptr(), B,
+                                                     pred[0].numel(), _stream_ptr(pred.device)), "disparity_metrics")
+    return epe, counts
 
 
 @torch.no_grad()
