@@ -4,7 +4,7 @@
 architecture, arch_spec.py — the reference's model code is not in the mount).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--variant voxel|point] [--dtype f32|bf16]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one forward of the hot path over one resident batch of B pairs per GPU (inputs already in
 HBM).  N>1: one process per GPU, the batch is sharded (weak scaling: B pairs per rank), and each step
@@ -13,9 +13,13 @@ collation.  `python bench.py --gpus N` launches its own N ranks (child `torch.di
 before anything touches the GPU); under an external launcher (WORLD_SIZE set) it is one of the ranks.
 Rank 0 prints ONE JSON line.
 
-Besides the headline (BASELINE configs[1]) the same process measures, untimed for `value`, the two other
-single-GPU configurations BASELINE.json names — configs[2] (bf16 MFMA path, batch 256) and configs[3]
-(Stereo2Point + Chamfer, batch 32) — and reports them under `secondary` (N=1 only; --no-secondary skips).
+A run does only what the headline (BASELINE configs[1]) needs: set-up, warm-up, the K timed steps,
+--dump-outputs and the line.  --full adds, after the timed steps and untimed for `value`: the per-step
+spread (`step_ms_spread`), the per-kernel roofline from an eager re-run of the same K steps (`roofline`,
+`kernels`; --no-profile skips it), and at N=1 the CPU oracle baseline (`cpu_baseline`; --no-cpu-baseline
+skips it) and, under `secondary` (--no-secondary skips them), the two other single-GPU configurations
+BASELINE.json names — configs[2] (bf16 MFMA path, batch 256) and configs[3] (Stereo2Point + Chamfer,
+batch 32) — beside configs[4]'s per-rank fp32 batch 256 and three batches in flight.
 """
 import argparse
 import glob
@@ -40,7 +44,10 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0    # dense bf16 MFMA peak (MI355X_MICROARCH.md; t
 PEAK_HBM_GBS = 8000.0
 PEAK_VALU_TLANE_INSTR = 78.6      # fp32 VALU issue: 256 CUs x 4 SIMDs x 32 lanes/clk x 2.4 GHz (= the 157.3 TFLOP/s vector peak / 2 FLOPs per FMA)
 ACHIEVABLE_HBM_GBS = 6300.0       # what a float4 copy kernel reaches on this chip (MI355X_MICROARCH.md: 6.29 TB/s measured, 79 %)
-SCHEMA = 5                        # of the JSON line.  5 (r05): + `roofline.aux`, `gemm_ms_per_step`, `frac_gemm_only`, `frac_useful`.
+SCHEMA = 6                        # of the JSON line.  6: + `full`; without --full `step_ms_spread` is null, `secondary` and
+                                  # `cpu_baseline` are absent, and a graph run's `roofline` / `kernels` are null / {} (a --no-graph
+                                  # run keeps the ones its timed steps' own events give).
+                                  # 5 (r05): + `roofline.aux`, `gemm_ms_per_step`, `frac_gemm_only`, `frac_useful`.
                                   # 4 (r04): `roofline.frac` = EXECUTED MFMA FLOPs / family kernel time / peak; through r03 (no
                                   # schema key) `frac` charged the direct form's FLOPs, which r04+ reports as `speedup_vs_direct_form`
                                   # (alias `frac_credited`): BENCH_r03 and BENCH_r04+ lines do not compare on `frac`
@@ -500,10 +507,14 @@ def main():
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="f32: exact-fp32 MFMA path (the headline, BASELINE configs[1]); bf16: bf16 MFMA path, "
                          "channels-last bf16 activations (configs[2], quoted at --batch 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the per-step spread, the "
+                         "per-kernel roofline (eager re-runs), and at N=1 the secondary configurations and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the configs[2] / configs[3] measurements that follow the headline at N=1")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
+                    help="with --full: skip the configs[2] / configs[3] measurements that follow the headline at N=1")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="do not bracket kernels with HIP events (the --no-graph timed steps, or --full's eager re-run)")
     ap.add_argument("--no-graph", action="store_true",
                     help="launch the ~20 kernels of a step eagerly instead of replaying the captured HIP graph")
     ap.add_argument("--include-h2d", action="store_true",
@@ -688,7 +699,7 @@ def main():
     # per-step spread (untimed for `value`): the same K steps once more, each bracketed by its own pair of events on
     # the launch stream — the timed region above is one interval, this shows what it averages over
     spread = None
-    if not dist_on:
+    if args.full and not dist_on:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
         for a, b in evs:
             a.record()
@@ -699,7 +710,7 @@ def main():
         spread = {"min": round(ts[0], 4), "median": round(ts[len(ts) // 2], 4), "max": round(ts[-1], 4)}
 
     eager_ms = None
-    if profiling and graphed is not None:                 # per-kernel HIP events: the same K steps again, eagerly (untimed)
+    if args.full and profiling and graphed is not None:   # per-kernel HIP events: the same K steps again, eagerly (untimed)
         records, eager_ms = eager_records(s3r, torch, model, left, right, gt_cloud, args.steps)
         records = records + aux_records(s3r, torch, model, left, right, gt_cloud, args.steps)
 
@@ -719,7 +730,7 @@ def main():
             except Exception:
                 rccl = None
         out = {
-            "schema": SCHEMA,
+            "schema": SCHEMA, "full": args.full,
             "metric": f"stereo pairs/s forward (batch {B}, 224x224 -> 32^3 voxel)" if args.variant == "voxel"
                       else f"stereo pairs/s forward (batch {B}, 224x224 -> 2048-pt cloud)",
             "value": round(value, 2), "unit": "stereo pairs/s", "n_gpus": world, "steps": args.steps,
@@ -738,8 +749,9 @@ def main():
             "kernel_env_overrides": overrides or None,
             "rccl_version": rccl,
             "end_to_end_tflops": round(value * fl["total"] / 1e12, 3),
-            "launch": "eager" if graphed is None else "hipGraph replay (1 launch per step); per-kernel HIP-event timing "
-                      "for `roofline` taken on an eager re-run of the same K steps right after the timed region",
+            "launch": "eager" if graphed is None else "hipGraph replay (1 launch per step)" +
+                      ("; per-kernel HIP-event timing for `roofline` taken on an eager re-run of the same K steps right after "
+                       "the timed region" if eager_ms else ""),
             "autotuned": {k: [v["tile"], v["ksplit"]] for k, v in tuned.items()} if tuned else None,
             "roofline": roof, "kernels": kernels,
         }
@@ -749,7 +761,7 @@ def main():
             # eager step (<= eager_step_ms) and may exceed the graph step by what the graph saves in gaps
             roof["graph_step_ms"] = round(ms_per_step, 4)
             roof["eager_minus_graph_step_ms"] = round(eager_ms - ms_per_step, 4)
-        if not dist_on and not args.no_secondary and args.variant == "voxel" and args.dtype == "f32" and \
+        if args.full and not dist_on and not args.no_secondary and args.variant == "voxel" and args.dtype == "f32" and \
                 not args.include_h2d and args.renders == "f32":
             # BASELINE.json configs[2] and configs[3], measured in the same process (never part of `value`)
             graphed = None                           # (its buffers stay with the model; the secondaries build their own)
@@ -770,7 +782,7 @@ def main():
                 log(f"secondary in_flight3_b32 failed: {type(e).__name__}: {e}")
                 sec["in_flight3_b32"] = {"error": f"{type(e).__name__}: {e}"}
             out["secondary"] = sec
-        if world == 1 and not args.no_cpu_baseline and not args.force_dist:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.force_dist:
             out["cpu_baseline"] = cpu_baseline(32)
         if outputs is not None:
             dump_outputs(args.dump_outputs, outputs)

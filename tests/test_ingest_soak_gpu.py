@@ -211,7 +211,7 @@ def test_bench_force_dist_builds_an_rccl_communicator_of_one_rank():
 def test_bench_global_batch_flag_and_runner_force_dist():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--global-batch", "6", "--steps", "2", "--warmup",
-                          "1", "--no-secondary", "--no-cpu-baseline", "--renders", "u8"], capture_output=True, text=True,
+                          "1", "--full", "--no-secondary", "--no-cpu-baseline", "--renders", "u8"], capture_output=True, text=True,
                          timeout=450, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

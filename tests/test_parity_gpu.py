@@ -768,15 +768,17 @@ def test_bench_ranks_share_one_gpu(tmp_path, launcher, world):
 
 
 def test_bench_line_carries_roofline_border_excluded_and_secondaries(tmp_path):
-    """The default N=1 line: roofline with frac and frac_border_excluded, no PMC constants unless the committed
+    """The N=1 line of a --full run: roofline with frac and frac_border_excluded, no PMC constants unless the committed
     counter file matches the sources that ran, and the configs[2] / configs[3] measurements under `secondary`."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if not k.startswith("S3R_")}      # the DEFAULT line: no kernel-policy overrides
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                          "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=500, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["full"] is True and 0 < d["step_ms_spread"]["min"] <= d["step_ms_spread"]["median"] <= d["step_ms_spread"]["max"]
     r = d["roofline"]
     # `frac` is what the matrix cores EXECUTE over their peak (<= 1: the pipe's utilisation); `frac_credited` charges the same
     # time with the direct form's FLOPs (with most convolutions on the Winograd kernels it may pass 1)
@@ -798,6 +800,29 @@ def test_bench_line_carries_roofline_border_excluded_and_secondaries(tmp_path):
     assert sec["point_b32"]["value"] > 0 and "chamfer" in sec["point_b32"]["kernels"] and "linear" in sec["point_b32"]["kernels"]
     # three independent batches in flight on three streams: the same work per step, never the headline; not slower than 0.9 x it
     assert sec["in_flight3_b32"]["streams"] == 3 and sec["in_flight3_b32"]["value"] > 0.9 * d["value"]
+
+
+@pytest.mark.timeout(300)
+def test_bench_without_full_measures_the_headline_alone():
+    """`python bench.py --steps K --warmup W` without --full: set-up, warm-up, the K timed steps and the line, nothing after
+    them, and at most 30 s of the whole run (start to exit of its own process) outside its K + W steps."""
+    import json, os, subprocess, sys, time
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if not k.startswith("S3R_")}
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=250, cwd=root, env=env)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["full"] is False and d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "stereo pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["metric"] == "stereo pairs/s forward (batch 32, 224x224 -> 32^3 voxel)"
+    assert d["step_ms_spread"] is None and d["roofline"] is None and d["kernels"] == {}
+    assert "secondary" not in d and "cpu_baseline" not in d
+    assert wall - 4 * d["ms_per_step"] / 1e3 < 30, wall
 
 
 @pytest.mark.timeout(500)

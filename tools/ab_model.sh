@@ -5,8 +5,8 @@
 OUT=$1; shift
 mkdir -p $OUT
 for i in 1 2 3; do
-  S3R_LIB=$PWD/tools/alt/base.so python bench.py --no-secondary --no-cpu-baseline "$@" > $OUT/base$i.json 2> $OUT/base$i.err
-  python bench.py --no-secondary --no-cpu-baseline "$@" > $OUT/new$i.json 2> $OUT/new$i.err
+  S3R_LIB=$PWD/tools/alt/base.so python bench.py --full --no-secondary --no-cpu-baseline "$@" > $OUT/base$i.json 2> $OUT/base$i.err
+  python bench.py --full --no-secondary --no-cpu-baseline "$@" > $OUT/new$i.json 2> $OUT/new$i.err
 done
 python - "$OUT" "${LAYERS:-}" <<'PY'
 import json, sys, glob

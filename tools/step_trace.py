@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """One forward step as the sequence of its kernels: reads a rocprofv3 --kernel-trace CSV of bench.py, cuts the dispatch list at
 the stem kernel and prints the median duration of every position of the step (name, us), in launch order.
-    rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary
+    rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary
     python3 tools/step_trace.py /tmp/tr"""
 import csv, glob, statistics, sys
 
