@@ -1,0 +1,340 @@
+"""The cases of tests/test_exact_gpu.py, shared with the harness's self-test in tests/test_exact_cpu.py.
+
+A case is a descriptor (layer, size, batch, dtype, tile, split-K, algo, halos) plus the recipe of its lattice data (`data`: what
+tests/_lattice.py::lattice_case takes).  Cases that differ only in HOW the layer is launched share their data, and with it the
+reference and the CPU self-test.
+"""
+from __future__ import annotations
+
+import dataclasses
+import math
+from dataclasses import dataclass
+
+import s3r
+import torch
+from s3r import arch_spec as spec
+
+from tests import _buffer_cases as BC
+from tests import _lattice as LT
+from tests import _ref64 as R
+
+L = spec.Layer
+DIRECT, WINO = s3r.ALGO_DIRECT, s3r.ALGO_WINOGRAD
+
+
+@dataclass(frozen=True)
+class Data:
+    layer: L
+    B: int
+    n_in: int
+    seed: int
+    form: str = "direct"
+    xmax: int = 2
+    wmax: int = 1
+    density: float = 1.0
+    dtype: str = "fp32"
+    xdensity: float = 1.0
+
+    def make(self):
+        return LT.lattice_case(self.layer, self.B, self.n_in, self.seed, self.form, self.xmax, self.wmax, self.density, self.xdensity)
+
+    @property
+    def bf16_out(self):
+        return self.dtype == "bf16" and not BC._head(self.layer, self.n_in)
+
+    @property
+    def id(self):
+        l = self.layer
+        return (f"{l.name}-{l.op}-{l.cin}to{l.cout}-k{l.k}s{l.s}p{l.p}d{l.dil}o{l.opad}-{l.act}{l.act_param or ''}-e{self.n_in}-B{self.B}-"
+                f"{self.dtype}-{self.form}-x{self.xmax}w{self.wmax}-s{self.seed}")
+
+
+@dataclass(frozen=True)
+class XCase:
+    id: str
+    data: Data
+    tile: int = -1
+    ksplit: int = 0
+    algo: int = 0
+    in_halo: int = -1          # -1: what the layer's kernel needs
+    out_halo: int = 0
+    refused: bool = False      # the library refuses this configuration: asserted refused, never launched
+    twice: bool = False        # also run over zero-filled scratch (descriptors tests/test_buffers_gpu.py does not run)
+
+    layer = property(lambda self: self.data.layer)
+    n_in = property(lambda self: self.data.n_in)
+    B = property(lambda self: self.data.B)
+    dtype = property(lambda self: self.data.dtype)
+
+
+def network():
+    rows = []
+    for layers, n0 in ((spec.ENCODER, spec.IMG_HW), (spec.DECODER, spec.MAX_DISP)):
+        rows += [(l, n) for l, n, _ in spec.trace(layers, n0)]
+    return rows
+
+
+def _bf16_data(layer, B, n_in, seed):
+    a, b = LT.bf16_magnitudes(R.k_terms(layer))
+    return Data(layer, B, n_in, seed, xmax=a, wmax=b, dtype="bf16")
+
+
+# ---------------------------------------------------------------- direct fp32
+def _direct_fp32():
+    cases = []
+    # all 18 network layers at their own sizes; the head with act none and ReLU (its sigmoid cannot be exact)
+    for i, (l, n) in enumerate(network()):
+        variants = [l] if l.act != "sigmoid" else [dataclasses.replace(l, act="none"), dataclasses.replace(l, act="relu")]
+        for lv in variants:
+            for B in (1, 3):
+                cases.append(XCase(f"{lv.name}-{lv.act}-B{B}", Data(lv, B, n, 100 + i), algo=DIRECT))
+    # tests/test_parity_gpu.py::test_every_tile_configuration: nine shapes x 8 tiles x both gather widths
+    for kind, (l, n, B, _) in {
+        "conv3d_s1": (L("t", "conv3d", 32, 96, 3, 1, 1), 7, 3, 0),
+        "conv3d_s1_w8": (L("t", "conv3d", 32, 96, 3, 1, 1), 8, 3, 0),
+        "conv3d_s2": (L("t", "conv3d", 16, 160, 3, 2, 1), 9, 2, 0),
+        "deconv": (L("t", "deconv3d", 32, 48, 4, 2, 1), 5, 3, 0),
+        "deconv_w4": (L("t", "deconv3d", 32, 48, 4, 2, 1), 4, 3, 0),
+        "conv2d_s2": (L("t", "conv2d", 48, 64, 3, 2, 1), 13, 5, 0),
+        "conv2d_s1_w12": (L("t", "conv2d", 48, 64, 3, 1, 1), 12, 5, 0),
+        "conv3d_k4_valid": (L("t", "conv3d", 16, 40, 4, 1, 0), 7, 2, 0),
+    }.items():
+        d = Data(l, B, n, 200)
+        out_w = n if l.op == "deconv3d" else spec.out_size(l, n)
+        for vec in (0, 1):
+            dword = vec == 1 or (l.op != "deconv3d" and l.s != 1) or out_w % 4 != 0
+            for tile in range(8):
+                # (the 64 x 512 tile is wider than one dword-gather row piece allows: refused, as that test expects)
+                cases.append(XCase(f"tile{tile}-vec{vec}-{kind}", d, tile=tile + 16 * vec, algo=DIRECT, refused=tile == 5 and dword, twice=True))
+    # tests/test_parity_gpu.py::test_split_k's shapes (their sigmoid replaced), and v5, v6, d1 at network size under forced split-K
+    for kind, (l, n, B) in {
+        "conv3d_k4_valid": (L("t", "conv3d", 64, 40, 4, 1, 0), 7, 3),
+        "deconv": (L("t", "deconv3d", 64, 48, 4, 2, 1), 5, 3),
+        "conv3d_s2": (L("t", "conv3d", 128, 160, 3, 2, 1, bn=False, act="none"), 9, 2),
+    }.items():
+        for ks in (1, 2, 4):
+            cases.append(XCase(f"splitk{ks}-{kind}", Data(l, B, n, 300), ksplit=ks, algo=DIRECT, twice=True))
+    net = dict((l.name, (l, n)) for l, n in network())
+    for name in ("v5", "v6", "d1"):
+        l, n = net[name]
+        for ks in (1, 2, 4, 8, 16):                    # cin / 16 >= 16 chunks: every power of two up to 16 divides them
+            cases.append(XCase(f"splitk{ks}-{name}-network", Data(l, 1, n, 310), ksplit=ks, algo=DIRECT, twice=True))
+    # the general-layer families of tests/_buffer_cases.py with an exact activation substituted
+    for c in BC.CONV_CASES:
+        fam = c.id.split("-")[0]
+        if c.dtype != "fp32" or fam not in ("general", "staged", "tclass", "unfolded", "d2s", "dilated", "leaky", "tanh", "elu", "head"):
+            continue
+        l = LT.exact_act(c.layer)
+        # (with its Tanh replaced, AUTO would pick a Winograd form for that layer, and this data is on the direct lattice)
+        algo = DIRECT if BC.has_wino(dataclasses.replace(c, layer=l)) else c.algo
+        cases.append(XCase("g-" + c.id, Data(l, c.B, c.n_in, 400), tile=c.tile, ksplit=c.ksplit, algo=algo, in_halo=c.in_halo,
+                           out_halo=c.out_halo))
+    # LeakyReLU: slope 1/2 fused in the split-K finish, slope 2 (> 1: the separate pass) behind a direct and a staged layer
+    cases += [
+        XCase("leaky-half-splitk2-finish", Data(L("t", "conv3d", 64, 32, 3, 2, 1, True, "leaky_relu", 1, 0, 0.5), 2, 9, 410), ksplit=2, twice=True),
+        XCase("leaky-2-pass-conv3d", Data(L("t", "conv3d", 32, 32, 3, 1, 1, True, "leaky_relu", 1, 0, 2.0), 2, 8, 411), algo=DIRECT, twice=True),
+        XCase("leaky-2-pass-staged-conv2d", Data(L("t", "conv2d", 20, 33, 5, 1, 2, True, "leaky_relu", 1, 0, 2.0), 2, 9, 412), twice=True),
+    ]
+    return cases
+
+
+DIRECT_CASES = _direct_fp32()
+
+# ---------------------------------------------------------------- linear
+LIN_SHAPES = [(32, 8192, 1024), (5, 1024, 6144), (33, 96, 40), (3, 50, 7), (70, 4096, 100), (4, 1, 9), (3, 7, 1), (2, 64, 7),
+              (7, 7, 7), (1, 256, 1), (32, 32768, 1024)]
+
+
+def _linear():
+    out = []
+    for B, cin, cout in LIN_SHAPES:
+        for act in ("none", "relu"):
+            # (K = 1, 7: a wider weight range, so that enough outputs clear the ReLU and differ from their neighbours)
+            out.append(XCase(f"linear-{B}x{cin}x{cout}-{act}", Data(L("t", "linear", cin, cout, 1, 1, 0, False, act), B, 1, 500,
+                                                                    wmax=1 if cin > 7 else 4), twice=cin == 32768))
+    for i, l in enumerate(spec.POINT_HEAD):
+        for B in (1, 3):
+            out.append(XCase(f"{l.name}-B{B}", Data(l, B, 1, 510 + i), twice=True))
+    return out
+
+
+LINEAR_CASES = _linear()
+
+# ---------------------------------------------------------------- bf16
+BF16_KINDS = {
+    "conv3d_s1": (L("t", "conv3d", 32, 96, 3, 1, 1), 7, 3, 0),
+    "conv3d_s2": (L("t", "conv3d", 64, 160, 3, 2, 1), 9, 2, 0),
+    "deconv": (L("t", "deconv3d", 32, 48, 4, 2, 1), 5, 3, 0),
+    "conv2d_s2": (L("t", "conv2d", 64, 64, 3, 2, 1), 13, 5, 0),
+    "conv3d_k4_valid_ks2": (L("t", "conv3d", 64, 40, 4, 1, 0), 7, 2, 2),
+    "cout32": (L("t", "conv2d", 256, 32, 1, 1, 0), 9, 3, 4),
+    "conv2d_s1_w28": (L("t", "conv2d", 64, 64, 3, 1, 1), 28, 3, 0),
+    "conv3d_s1_w14": (L("t", "conv3d", 32, 64, 3, 1, 1), 14, 2, 0),
+    "conv3d_s1_c64": (L("t", "conv3d", 64, 96, 3, 1, 1), 7, 3, 0),
+    "deconv_c64": (L("t", "deconv3d", 64, 48, 4, 2, 1), 5, 3, 0),
+    "deconv_c128_w8": (L("t", "deconv3d", 128, 64, 4, 2, 1), 8, 2, 0),
+    "conv3d_k4_valid_c128_ks2": (L("t", "conv3d", 128, 40, 4, 1, 0), 7, 2, 2),
+    "conv2d_s1_c128_w9": (L("t", "conv2d", 128, 64, 3, 1, 1), 9, 21, 0),
+    "cout36_narrow_stores": (L("t", "conv2d", 64, 36, 3, 1, 1), 9, 3, 0),
+    "cout100_s2": (L("t", "conv3d", 32, 100, 3, 2, 1), 9, 2, 0),
+    "c128_cout128_ks2": (L("t", "conv3d", 128, 128, 3, 1, 1), 6, 2, 2),
+}
+BF16_TILES = (1, 2, 3, 4, 5, 6, 9, 10, 17, 18, 19, 21, 22, 23)
+
+
+def bf16_refused(tm, kind):
+    """tests/test_bf16_gpu.py::test_bf16_tiles_and_split_k's refusal rules, verbatim"""
+    layer, n_in, B, ks = BF16_KINDS[kind]
+    kc = 64 if tm in (5, 6) else 32
+    plane_ok = (layer.s == 1 or layer.op == "deconv3d") and layer.cin % kc == 0 and (ks == 0 or (layer.cin // kc) % ks == 0)
+    if tm in (6, 22, 23) and kind in ("conv3d_k4_valid_c128_ks2", "conv3d_k4_valid_ks2"):
+        plane_ok = False
+    if tm == 6 and kind == "c128_cout128_ks2":
+        plane_ok = False
+    wide_ok = (-(-layer.cout // 64)) % 2 == 0
+    return (tm == 10 and kind in ("conv3d_s2", "cout100_s2")) or (tm in (5, 6, 21, 22, 23) and not plane_ok) or \
+        (tm in (3, 19, 23) and not wide_ok)
+
+
+def _bf16():
+    cases = []
+    for i, (l, n) in enumerate(network()):
+        lv = dataclasses.replace(l, act="none") if l.act == "sigmoid" else l
+        for B in (1, 3):
+            cases.append(XCase(f"{lv.name}-bf16-B{B}", _bf16_data(lv, B, n, 600 + i)))
+    for kind, (l, n, B, ks) in BF16_KINDS.items():
+        d = _bf16_data(l, B, n, 700)
+        for tm in BF16_TILES:
+            cases.append(XCase(f"bf16-tile{tm}-{kind}", d, tile=tm, ksplit=ks, refused=bf16_refused(tm, kind), twice=True))
+    return cases
+
+
+BF16_CASES = _bf16()
+
+
+
+# ---------------------------------------------------------------- Winograd fp32 (weights on the form's lattice)
+def _wino_data(layer, B, n_in, seed, form):
+    """two-axis F(4, 3) x F(4, 3): the flow through |B^T|, |G|, the channel sum and |A^T| grows with cin x (taps left in a class) and
+    must stay below 2^24 (tests/_lattice.py::exactness), so x and w are thinned by sqrt(50 / that) each; x in {-1, 0, 1} throughout"""
+    units = layer.cin * (3 if layer.op == "conv3d" else 1)
+    dn = min(1.0, round(math.sqrt(50 / units), 2)) if form == "f43x2" else 1.0
+    return Data(layer, B, n_in, seed, form, xmax=1, wmax=1, density=dn, xdensity=dn)
+
+
+def _wino():
+    cases = []
+    net = dict((l.name, (l, n)) for l, n in network())
+    names = {0: "serial", 1: "class-parallel", 2: "dual"}
+    # one axis, F(4, 3) along H, in its three launch forms
+    for tag, l, n, B in (("conv2d-32to48-e40", L("t", "conv2d", 32, 48, 3, 1, 1), 40, 3), ("conv3d-64to64-e12", L("t", "conv3d", 64, 64, 3, 1, 1), 12, 2),
+                         ("e2", *net["e2"], 2), ("e4", *net["e4"], 2)):
+        d = _wino_data(l, B, n, 800, "f43-h")
+        for t in (0, 1, 2):
+            cases.append(XCase(f"wino1-{names[t]}-{tag}", d, tile=t, algo=WINO, twice=tag in ("e2", "e4")))
+    # two axes: 3 the two-axis algorithm, 4 its class-parallel form, 5 its semi-fused form
+    for tag, l, n, B in (("e6", *net["e6"], 2), ("e7", *net["e7"], 2), ("conv2d-64to96-e20", L("t", "conv2d", 64, 96, 3, 1, 1), 20, 3),
+                         ("v1", *net["v1"], 2), ("v3", *net["v3"], 2), ("v5", *net["v5"], 2)):
+        d = _wino_data(l, B, n, 810, "f43x2")
+        for t in (3, 4, 5):
+            cases.append(XCase(f"wino2-tile{t}-{tag}", d, tile=t, algo=WINO, twice=len(tag) == 2))
+    d = _wino_data(net["v6"][0], 2, net["v6"][1], 820, "f24x2")
+    for t in (3, 4, 5):                                # (F(2, 4) x F(2, 4) has no semi-fused form: tile 5 is refused)
+        cases.append(XCase(f"wino2-tile{t}-v6", d, tile=t, algo=WINO, refused=t == 5, twice=True))
+    # transposed: F(2, 2) along D and H inside the parity classes (the library's pick and the three launch forms), and the three-axis form
+    for name in ("d1", "d2"):
+        l, n = net[name]
+        d = Data(l, 2, n, 830, "f22x2")
+        for t in (-1, 0, 1, 2):
+            cases.append(XCase(f"dwino-tile{t}-{name}", d, tile=t, algo=WINO, twice=True))
+    t3 = L("t", "deconv3d", 64, 32, 4, 2, 1)
+    for n in (8, 16):
+        d = Data(t3, 2, n, 840, "f22x3")
+        for t in (6, 7, 8):
+            cases.append(XCase(f"wino3-tile{t}-deconv3d-64to32-e{n}", d, tile=t, algo=WINO))
+    cases.append(XCase("wino3-tile6-d3", Data(net["d3"][0], 1, net["d3"][1], 841, "f22x3"), tile=6, algo=WINO, twice=True))
+    return cases
+
+
+WINO_CASES = _wino()
+
+# ---------------------------------------------------------------- producers that hand a consumer its input: cost volume, chains
+@dataclass(frozen=True)
+class CVCase:
+    """s3r_cost_volume_forward_wino / _wino2 writing v1's transformed planes (in_layout), v1 on the form's lattice.  The features are
+    integers in {-1, 0, 1}, the volume their differences in {-2 .. 2}: exact, and on v1's input lattice"""
+    id: str
+    kind: str                  # "wino": six F(4, 3)-along-H plane sets, "wino2": the 36 two-axis ones
+    B: int
+    seed: int
+    fdensity: float
+    data: Data                 # v1's (the cost volume stands in for its x)
+
+    def features(self):
+        g = torch.Generator().manual_seed(self.seed)
+        shape = (self.B, spec.FEAT_C, spec.FEAT_HW, spec.FEAT_HW)
+        return tuple(torch.randint(-1, 2, shape, generator=g).float() * (torch.rand(shape, generator=g) < self.fdensity).float() for _ in range(2))
+
+    def make(self):
+        """(volume, v1's parameters): the volume from the oracle's own formulation, exact on integers"""
+        from oracle import s2v_oracle as O
+        _, p = self.data.make()
+        return O.cost_volume(*self.features(), spec.MAX_DISP), p
+
+
+def _cv():
+    v1, n = dict((l.name, (l, n)) for l, n in network())["v1"]
+    return [CVCase("cost-volume-wino->v1", "wino", 2, 900, 1.0, _wino_data(v1, 2, n, 901, "f43-h")),
+            # (|x| up to 2 doubles the two-axis flow: the features are thinned to a third, on top of v1's own thinning)
+            CVCase("cost-volume-wino2->v1", "wino2", 2, 910, 0.35, _wino_data(v1, 2, n, 911, "f43x2"))]
+
+
+CV_CASES = _cv()
+
+
+@dataclass(frozen=True)
+class ChainCase:
+    """two layers through s3r_chain_forward; the first has scale 1 / shift 0 / ReLU, so the intermediate stays on the integer lattice"""
+    id: str
+    first: Data
+    second: Data               # (its x is the first layer's output: only the parameters of second.make() are used)
+    dtype: str = "fp32"
+
+    def make(self):
+        x, p0 = self.first.make()
+        p0 = dict(p0, scale=None if p0["scale"] is None else torch.ones_like(p0["scale"]), shift=torch.zeros_like(p0["shift"]))
+        _, p1 = self.second.make()
+        return x, [p0, p1]
+
+    def intermediate(self, x, p0):
+        """the first layer's exact output in the second layer's geometry (rounded to bf16 on that path: exact when |h| <= 256)"""
+        h = LT.expected(self.first.layer, x, p0, "fp32")
+        return h.to(torch.bfloat16).float() if self.dtype == "bf16" else h
+
+
+def _chains():
+    net = dict((l.name, (l, n)) for l, n in network())
+    (e1, n1), (e2, n2), (d3, n3), (d4, n4) = net["e1"], net["e2"], net["d3"], net["d4"]
+    head = dataclasses.replace(d4, act="none")
+    return [
+        # the stem writes e2's F(4, 3)-along-H plane sets (the library's own pick for this pair): e2 on that form's lattice
+        ChainCase("stem->e2", Data(e1, 2, n1, 920, xmax=1), _wino_data(e2, 2, n2, 921, "f43-h")),
+        # bf16: d3 with the head fused into its launch (d3's output is never materialised).  d3's data is thinned until its output stays
+        # within +-256, where bf16 holds every integer: the intermediate is then the same number whether or not the kernel rounds it
+        ChainCase("d3+head-bf16", Data(d3, 2, n3, 930, xmax=1, density=0.25, xdensity=0.25, dtype="bf16"), Data(head, 2, n4, 931, wmax=2, dtype="bf16"),
+                  dtype="bf16"),
+    ]
+
+
+CHAIN_CASES = _chains()
+
+ALL_CASES = DIRECT_CASES + LINEAR_CASES + BF16_CASES + WINO_CASES
+
+
+def unique_data(cases=None):
+    seen, out = set(), []
+    for c in (ALL_CASES if cases is None else cases):
+        if c.data not in seen:
+            seen.add(c.data)
+            out.append(c.data)
+    return out

@@ -19,8 +19,11 @@ and (K + 3) u (1.01) covers both terms.  The activation is L-Lipschitz (ReLU / n
 ELU max(1, alpha)), and its own evaluation in fp32 adds a_act: 0 for ReLU / none, u |ref| for LeakyReLU, 8 u (|ref| + max(1, alpha))
 for the transcendental ones (a few ulp of expf / tanhf / the divide).  `tiny` = 2^-120 covers the underflow range.
 
-This is a worst-case (not a statistical) bound, so it is safe; it is also tight enough to see one missing or doubled tap: the
-mutation self-test in tests/test_buffers_cpu.py builds those errors in fp32 for every case and requires the checker to flag them.
+This is a worst-case (not a statistical) bound, so it is safe; it is also tight enough to see one missing or doubled TAP (all cin
+terms of it): the mutation self-test in tests/test_buffers_cpu.py builds those errors in fp32 for every case and requires the
+checker to flag them.  It cannot see one TERM — a single (channel, tap) product is about mag / K and the bound grows with K, so
+from a few thousand terms on a dropped or doubled one is inside it (tests/test_exact_cpu.py asserts that for K >= 16384).  Single
+terms are held bit for bit, on integer-lattice data, by tests/test_exact_gpu.py (tests/_lattice.py).
 
 Winograd forms (one-, two-, three-axis; form "wino"): the transforms mix a tile, so an element's error follows its neighbours'
 magnitudes.  The bound is 5e-5 L max_{neighbourhood}(mag) + a_act + tiny — the constant of tests/test_wino_gpu.py::

@@ -18,9 +18,9 @@ import torch
 from tests import _buffer_cases as BC
 from tests import _guard as G
 from tests import _ref64 as R
+from tests._abi_calls import DEV, interior as _interior, pack as _pack, pad as _pad, rc_ok as _rc, sync as _sync
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 HALF = 0.5
 
 
@@ -29,56 +29,11 @@ def lib(s3r):
     return s3r.load_library()
 
 
-def _sync():
-    torch.cuda.synchronize()
-
-
-def _rc(lib, rc, what):
-    assert rc == 0, f"{what}: {lib.s3r_last_error().decode()} ({rc})"
-
-
-def _pad(x, h, cl=False):
-    """zero-halo buffer of logical x (B, C, *sp); channels-last (B, *sp, C) when cl"""
-    if cl:
-        x = x.permute(0, *range(2, x.dim()), 1)
-        sp = tuple(range(1, x.dim() - 1))
-    else:
-        sp = tuple(range(2, x.dim()))
-    shape = list(x.shape)
-    for d in sp:
-        shape[d] += 2 * h
-    out = torch.zeros(shape, dtype=x.dtype, device=x.device)
-    idx = [slice(None)] * x.dim()
-    for d in sp:
-        idx[d] = slice(h, h + x.shape[d])
-    out[tuple(idx)] = x
-    return out, sp
-
-
-def _interior(y, h, sp, cl):
-    idx = [slice(None)] * y.dim()
-    for d in sp:
-        idx[d] = slice(h, y.shape[d] - h)
-    t = y[tuple(idx)]
-    return t.permute(0, t.dim() - 1, *range(1, t.dim() - 1)) if cl else t
-
-
 def _check_values(layer, form, got, ref, mag, what):
     bnd = R.bound(layer, ref, mag, form)
     ratio, i = R.worst(got, ref, bnd)
     print(f"\nratio {form} {ratio:.3e} {what}")
     assert ratio <= HALF, (what, form, ratio, i, float(got.reshape(-1)[i]), float(ref.reshape(-1)[i]), float(bnd.reshape(-1)[i]))
-
-
-def _pack(lib, s3r, desc, w, name="packed"):
-    n = C.c_int64(0)
-    _rc(lib, lib.s3r_conv_packed_elems(C.byref(desc), C.byref(n)), "packed_elems")
-    wb = G.Guarded("w", w.shape, torch.float32, DEV, "in", data=w)
-    pk = G.Guarded(name, n.value, torch.float32, DEV, "out")
-    _rc(lib, lib.s3r_conv_pack_weights(C.byref(desc), wb.ptr, pk.ptr, None), "pack_weights")
-    _sync()
-    G.check_all(wb, pk)
-    return pk, wb
 
 
 # ---------------------------------------------------------------- s3r_conv_pack_weights + s3r_conv_forward
@@ -308,7 +263,8 @@ def test_cost_volume_planes(s3r, lib, shape, kind):
 
 
 # ---------------------------------------------------------------- linear
-# (test_linear_layer's (32, 32768, 1024) at K = 8192: at K = 32768 one dropped term hides below the bound, tests/_ref64.py)
+# (the bound sees a dropped TAP; single terms, and test_linear_layer's (32, 32768, 1024) at its full K, are held bit for bit on
+# the integer lattice by tests/test_exact_gpu.py)
 LIN_SHAPES = [(32, 8192, 1024), (5, 1024, 6144), (33, 96, 40), (3, 50, 7), (70, 4096, 100), (4, 1, 9), (3, 7, 1), (2, 64, 7),
               (7, 7, 7), (1, 256, 1)]
 

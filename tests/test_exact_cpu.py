@@ -1,0 +1,179 @@
+"""Host-side half of tests/test_exact_gpu.py: the lattice harness proves itself without a GPU.
+
+For the data of every case of the GPU file: the case is admissible (tests/_lattice.py::exactness, conditions computed from the
+reference alone), and the comparison it allows — bit equality with `expected` — catches, on the CPU restatement of the layer in
+fp32, ONE (channel, tap) weight zeroed, one doubled, one output shifted by a position, and on bf16 outputs a conversion that
+truncates or rounds halves away from zero.  For the deep layers (K >= 16384: p1, v6, the 32768-wide linear shape) the two
+single-term mutants are also shown to be INVISIBLE to tests/_ref64.py's bound — the reason this file exists.  Which
+configurations the library refuses is checked against its planner (host only).
+"""
+import ctypes as C
+import dataclasses
+import os
+
+import pytest
+import torch
+
+from tests import _buffer_cases as BC
+from tests import _exact_cases as X
+from tests import _lattice as LT
+from tests import _ref64 as R
+
+torch.set_num_threads(min(16, torch.get_num_threads()))
+DATA = X.unique_data()
+
+
+@pytest.fixture(scope="module")
+def lib(s3r):
+    import __graft_entry__ as g
+    if not os.path.exists(s3r.LIB_PATH):
+        g.build()
+    return s3r.load_library()
+
+
+# ---------------------------------------------------------------- admissibility
+@pytest.mark.parametrize("d", DATA, ids=[d.id for d in DATA])
+def test_case_is_admissible(d):
+    x, p = d.make()
+    rec = LT.exactness(d.layer, x, p, d.form, d.dtype)
+    print(f"\n{d.id}: " + " ".join(f"{k}={v:.4g}" if isinstance(v, float) else f"{k}={v}" for k, v in rec.items()))
+    assert LT.admissible(rec, d.bf16_out) is None, (LT.admissible(rec, d.bf16_out), rec)
+
+
+# ---------------------------------------------------------------- mutation self-test
+def _one_channel(layer, p, o):
+    w = p["w"]
+    w = w[:, o:o + 1] if layer.op.startswith("deconv") else w[o:o + 1]
+    return dataclasses.replace(layer, cout=1), {"w": w.clone(), "scale": None if p["scale"] is None else p["scale"][o:o + 1],
+                                                 "shift": p["shift"][o:o + 1]}
+
+
+def _term_with_effect(layer, x, p, active):
+    """flat index into w of ONE (channel, tap) term whose own contribution reaches an output that is non-zero after the activation"""
+    w = p["w"]
+    nz = w.reshape(-1).nonzero().reshape(-1)
+    order = nz[torch.randperm(nz.numel(), generator=torch.Generator().manual_seed(1))]
+    for t in order[:64].tolist():
+        single = torch.zeros_like(w)
+        single.reshape(-1)[t] = w.reshape(-1)[t]
+        if bool(((R.linmap(layer, x.double(), single.double()) != 0) & active).any()):
+            return t
+    raise AssertionError("no single term reaches an active output: the case cannot see a dropped term")
+
+
+def _rhaz_bf16(v):
+    """fp32 -> bf16 rounding halves AWAY from zero (add half a bf16 ulp to the magnitude, truncate)"""
+    b = v.contiguous().view(torch.int32)
+    return (((b & 0x7FFFFFFF) + 0x8000) & ~0xFFFF | (b & -2 ** 31)).view(torch.float32)
+
+
+def _trunc_bf16(v):
+    return (v.contiguous().view(torch.int32) & ~0xFFFF).view(torch.float32)
+
+
+@pytest.mark.parametrize("d", DATA, ids=[d.id for d in DATA])
+def test_bit_equality_catches_every_mutant(d):
+    _mutants_caught(d, *d.make())
+
+
+def _mutants_caught(d, xs, p):
+    """d: the Data whose layer / form / dtype apply; (xs, p): the layer's actual input and parameters"""
+    x = xs[:1]
+    for o in range(d.layer.cout // 2, d.layer.cout):            # (the first channel from the middle on that has an output above the ReLU)
+        l1, p1 = _one_channel(d.layer, p, o)
+        if bool((R.ref64(l1, x, p1)[0] != 0).any()):
+            break
+    want = LT.expected(l1, x, p1, "bf16" if d.bf16_out else "fp32")
+    bits = (lambda t: t.view(torch.int16)) if d.bf16_out else (lambda t: t.view(torch.int32))
+    to_out = (lambda t: t.to(torch.bfloat16)) if d.bf16_out else (lambda t: t)
+    clean = LT.fp32_layer(l1, x, p1)
+    assert torch.equal(bits(to_out(clean)), bits(want)), "the fp32 restatement itself differs from the reference"
+    ref, mag = R.ref64(l1, x, p1)
+    active = ref != 0
+    assert bool(active.any()), "no channel with an active output"
+    t = _term_with_effect(l1, x, p1, active)
+    deep = R.k_terms(d.layer) >= 16384 and d.form == "direct"      # (dense data: a Winograd case keeps one tap in 9 or 16)
+    bnd = R.bound(l1, ref, mag, "bf16" if d.bf16_out else ("direct" if d.form == "direct" else "wino"))
+    for name, f in (("zeroed", 0.0), ("doubled", 2.0)):
+        q = dict(p1, w=p1["w"].clone())
+        q["w"].reshape(-1)[t] *= f
+        m = LT.fp32_layer(l1, x, q)
+        assert not torch.equal(bits(to_out(m)), bits(want)), (name, "one term: not caught")
+        if deep and not d.bf16_out:
+            r, _ = R.worst(m, ref, bnd)
+            assert r <= 1.0, (name, "the fp64 bound was expected NOT to see one term at this K", r)
+    flat = clean.reshape(-1)
+    if flat.numel() > 1:
+        i = int((flat[1:] - flat[:-1]).abs().argmax())
+        s = flat.clone()
+        s[i] = flat[i + 1]
+        assert not torch.equal(bits(to_out(s.reshape(clean.shape))), bits(want)), "a shifted output: not caught"
+    if d.bf16_out:
+        full = LT.expected(d.layer, xs, p, "fp32")               # (the whole case: its share of ties is a condition on all of it)
+        for name, conv in (("truncation", _trunc_bf16), ("round-half-away", _rhaz_bf16)):
+            assert not torch.equal(conv(full).to(torch.bfloat16).view(torch.int16), full.to(torch.bfloat16).view(torch.int16)), \
+                (name, "not caught")
+
+
+# ---------------------------------------------------------------- producers: the cost volume in v1's layouts, two-layer chains
+@pytest.mark.parametrize("c", X.CV_CASES, ids=[c.id for c in X.CV_CASES])
+def test_cost_volume_case(c):
+    vol, p = c.make()
+    assert float(vol.abs().max()) <= 2 and bool((vol == vol.round()).all())
+    rec = LT.exactness(c.data.layer, vol, p, c.data.form)
+    print(f"\n{c.id}: {rec}")
+    assert LT.admissible(rec) is None, (LT.admissible(rec), rec)
+    _mutants_caught(c.data, vol, p)
+
+
+@pytest.mark.parametrize("c", X.CHAIN_CASES, ids=[c.id for c in X.CHAIN_CASES])
+def test_chain_case(c):
+    x, (p0, p1) = c.make()
+    assert (p0["scale"] is None or bool((p0["scale"] == 1).all())) and bool((p0["shift"] == 0).all()) and c.first.layer.act == "relu"
+    r0 = LT.exactness(c.first.layer, x, p0, c.first.form, c.dtype)
+    h = c.intermediate(x, p0)
+    r1 = LT.exactness(c.second.layer, h, p1, c.second.form, c.dtype)
+    print(f"\n{c.id}: {r0}\n{r1}")
+    # (the intermediate of the bf16 chain is never stored as bf16 data the test reads: no share of ties is asked of it, but it must
+    # be exact in bf16, so that rounding it or not is the same number)
+    assert LT.admissible(r0) is None and LT.admissible(r1) is None, (LT.admissible(r0), LT.admissible(r1))
+    if c.dtype == "bf16":
+        assert float(h.abs().max()) <= 256 and torch.equal(h, LT.expected(c.first.layer, x, p0))
+    _mutants_caught(dataclasses.replace(c.second, dtype="fp32"), h, p1)
+
+
+def test_rounding_mutants_are_what_they_say():
+    v = torch.tensor([257.0, 259.0, 258.5, -257.0, -259.0, 1.0, 300.25])           # 257: tie, even below; 259: tie, even above
+    assert _trunc_bf16(v).tolist() == [256.0, 258.0, 258.0, -256.0, -258.0, 1.0, 300.0]
+    assert _rhaz_bf16(v).tolist() == [258.0, 260.0, 258.0, -258.0, -260.0, 1.0, 300.0]
+    assert v.to(torch.bfloat16).float().tolist() == [256.0, 260.0, 258.0, -256.0, -260.0, 1.0, 300.0]
+    assert LT.bf16_shares(v) == (4 / 7, 2 / 7)
+
+
+def test_lattice_steps_come_from_the_matrices():
+    """F(4, 3) with the points 0, +-1, +-2, inf: 24; F(2, 4) with 0, +-1, 2, inf: 6 (computed, tools/wino_matrices.py's construction)"""
+    assert LT.wino_step("f43") == 24 and LT.wino_step("f24") == 6 and LT.wino_step("f22") == 1
+    for kind in ("f43", "f24"):
+        AT, G, BT = LT.wino_matrices(kind)
+        assert all(v.denominator == 1 for row in AT + BT for v in row), "B^T and A^T are integer matrices"
+
+
+# ---------------------------------------------------------------- refusals (host only: the planner)
+def _desc(s3r, c):
+    ih = c.in_halo if c.in_halo >= 0 else BC.need_halo(c.layer, c.n_in, c.dtype)
+    return s3r._lib.make_desc(c.layer, c.B, c.n_in, tile=c.tile, in_halo=ih, out_halo=c.out_halo, ksplit=c.ksplit,
+                              dtype=s3r._lib.DTYPE[c.dtype], algo=c.algo)
+
+
+CONV = [c for c in X.ALL_CASES if c.layer.op != "linear" and c.dtype == "fp32"]
+
+
+def test_refusals_match_the_planner(s3r, lib):
+    """fp32: a forced tile without its gather is refused by the scratch query, everything else plans (the bf16 path refuses a forced
+    tile when it resolves the launch: the GPU file asserts those)"""
+    wrong = []
+    for c in CONV:
+        d = _desc(s3r, c)
+        if (lib.s3r_conv_scratch_elems(C.byref(d)) < 0) != c.refused:
+            wrong.append((c.id, c.refused, lib.s3r_last_error()))
+    assert not wrong, wrong

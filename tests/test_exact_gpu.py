@@ -1,0 +1,300 @@
+"""Every convolution, linear and bf16 kernel against the float64 reference BIT FOR BIT, on integer-lattice data.
+
+tests/_lattice.py holds the argument: with the input, the weights and the folded epilogue on an integer (dyadic) lattice and the
+absolute-value flow below 2^24, no fp32 operation of ANY summation order rounds, so the kernel's output must equal the float64
+reference bit for bit; on the bf16 path it must equal RNE_bf16(exact value).  There is no tolerance, so one missing or doubled
+(channel, tap) term is a mismatch at any reduction depth — the network's p1 (K = 32768), v6 (16384), v5 (6912), d1 (4096) and
+the 32768-wide linear shape included, where tests/_ref64.py's bound cannot see a term.  tests/test_exact_cpu.py proves, without a
+GPU, that every case here is admissible and that bit equality catches the single-term, shifted-output and rounding-mode mutants.
+
+Bit patterns are compared (`view(int32)` / `view(int16)`), so -0.0 against +0.0 would be reported: the reference of no case holds a
+-0.0 (asserted on the CPU: the epilogue adds a +0.0-or-non-zero shift last), so the contract here is +0.0.
+
+Every call goes through the C-ABI (s3r_conv_pack_weights + s3r_conv_forward, s3r_linear_forward, s3r_chain_forward) with NaN-filled
+scratch and a NaN-filled output; the descriptors tests/test_buffers_gpu.py does not run (forced tiles and split-K, the bf16 tile
+matrix, the deep linear shapes) run a second time over zero-filled scratch.  Guards and poisons are that file's subject, values
+are this one's.  A configuration the library refuses (tests/test_parity_gpu.py's and tests/test_bf16_gpu.py's rules) is asserted
+refused — fp32 tiles by the scratch query, bf16 tiles by the forward call, which must return an error and leave the output
+untouched — and never compared.
+
+A mismatch is reported as the first differing element with its (b, cout, position), the exact value, the value got and their
+difference in lattice units (2^-f): a difference equal to one `w x` product names the tap.
+
+Cases: direct fp32 233 (18 network layers x B 1 / 3, 8 shapes x 8 tiles x 2 gather widths, split-K 1 / 2 / 4 and v5 / v6 / d1 at
+network size under split-K 1 .. 16, the general-layer families), linear 28, bf16 260 under each of the two matrix instructions
+(18 layers x B 1 / 3, the 14 x 16 tile matrix), Winograd 48 (one-axis x 3 launch forms, two-axis tiles 3 / 4 / 5 incl. F(2,4) x F(2,4),
+transposed F(2,2) classes and the three-axis form), the cost volume writing v1's plane sets in both layouts, the stem -> e2 hand-off,
+the bf16 d3 + head fused launch, and four runs that drop ONE term on the device and require the mismatch.  On an MI355X every one
+of them is bit-exact: the tests found no kernel or pack bug.
+
+Staying on tests/_ref64.py's bound (tests/test_buffers_gpu.py's chain matrix): the e6 -> e7 two-axis hand-off AS A CHAIN.  The
+producer's weights must be multiples of 576 (wax_g in s3r_conv_wino.hip folds 1/24 per axis into them), so the intermediate is
+a multiple of 576, and the consumer's weights bring another 576: one unit product is 3.3e5 and the flow passes 2^24 after a few
+dozen terms, whatever the data.  e6 and e7 are held exactly one at a time (wino2-tile3/4/5-e6, -e7).  The activations Sigmoid, ELU
+and Tanh stay there too (transcendental), and the 8-bit stem entry (it scales by 1/255; it is tied to the fp32 entry bit for bit).
+
+Wall time on an MI355X: `pytest tests -m gpu` without this file 144 s (1181 tests); this file 6 s (838 tests).
+"""
+import ctypes as C
+
+import pytest
+import torch
+
+from tests import _buffer_cases as BC
+from tests import _exact_cases as X
+from tests import _lattice as LT
+from tests._abi_calls import DEV, interior, pad, rc_ok, sync
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def lib(s3r):
+    return s3r.load_library()
+
+
+@pytest.fixture(params=[32, 16], ids=["mfma32x32x16", "mfma16x16x32"])
+def mfma_shape(request, monkeypatch):
+    """both matrix instructions the bf16 kernels are built for (S3R_BF16_MFMA, read per call)"""
+    monkeypatch.setenv("S3R_BF16_MFMA", str(request.param))
+    return request.param
+
+
+_DATA = {}
+
+
+def _data(d):
+    """(x, params, expected) of a case's data on the device; the reference in float64 on the device, kept for the cases that share it"""
+    if d not in _DATA:
+        if len(_DATA) >= 4:
+            _DATA.pop(next(iter(_DATA)))
+        x, p = d.make()
+        x = x.to(DEV)
+        p = {k: None if v is None else v.to(DEV) for k, v in p.items()}
+        _DATA[d] = (x, p, LT.expected(d.layer, x, p, "bf16" if d.bf16_out else "fp32"))
+    return _DATA[d]
+
+
+def assert_bits(got, want, d, p, what):
+    """bit equality, or the first differing element: (b, cout, position), exact, got, difference in lattice units"""
+    assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
+    view = torch.int16 if got.dtype == torch.bfloat16 else torch.int32
+    gb, wb = got.contiguous().view(view), want.contiguous().view(view)
+    if torch.equal(gb, wb):
+        return
+    bad = (gb != wb)
+    i = int(bad.reshape(-1).nonzero()[0, 0])
+    idx = tuple(int(v) for v in torch.unravel_index(torch.tensor(i), want.shape))
+    g, w = float(got.reshape(-1)[i]), float(want.reshape(-1)[i])
+    unit = 2.0 ** -LT.frac_bits(d.layer, p)
+    raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ; first at (b, cout, position) = "
+                         f"({idx[0]}, {idx[1] if len(idx) > 1 else '-'}, {idx[2:]}): exact {w!r}, got {g!r}, difference {(g - w) / unit!r} "
+                         f"lattice units of {unit}")
+
+
+def make_desc(s3r, c):
+    ih = c.in_halo if c.in_halo >= 0 else BC.need_halo(c.layer, c.n_in, c.dtype)
+    return ih, s3r._lib.make_desc(c.layer, c.B, c.n_in, tile=c.tile, in_halo=ih, out_halo=c.out_halo, ksplit=c.ksplit,
+                                  dtype=s3r._lib.DTYPE[c.dtype], algo=c.algo)
+
+
+def run_conv(s3r, lib, c):
+    """the case through s3r_conv_pack_weights + s3r_conv_forward; the logical (B, cout, ...) output"""
+    l, nd, bf = c.layer, LT.R.ndim(c.layer), c.dtype == "bf16"
+    ih, desc = make_desc(s3r, c)
+    need = lib.s3r_conv_scratch_elems(C.byref(desc))
+    if c.refused and not bf:                          # fp32: the planner refuses the descriptor (checked on the CPU too)
+        assert need == -1 and lib.s3r_last_error(), (c.id, "expected to be refused", need)
+        return None
+    assert need >= 0, (c.id, lib.s3r_last_error())
+    x, p, _ = _data(c.data)
+    n = C.c_int64(0)
+    rc_ok(lib, lib.s3r_conv_packed_elems(C.byref(desc), C.byref(n)), "packed_elems")
+    w = p["w"].contiguous()
+    pk = torch.full((n.value,), float("nan"), device=DEV)
+    rc_ok(lib, lib.s3r_conv_pack_weights(C.byref(desc), w.data_ptr(), pk.data_ptr(), None), "pack_weights")
+    cl_in, cl_out = bf and not BC._stem(l), bf and not BC._head(l, c.n_in)
+    xp, _ = pad(x.to(torch.bfloat16) if cl_in else x, ih, cl_in)
+    xp = xp.contiguous()
+    n_out = lib.s3r_conv_out_size(C.byref(desc))
+    oh = c.out_halo
+    ysp = (n_out + 2 * oh,) * nd
+    yshape = (c.B,) + ysp + (l.cout,) if cl_out else (c.B, l.cout) + ysp
+    sp = tuple(range(1, 1 + nd)) if cl_out else tuple(range(2, 2 + nd))
+    sc = None if p["scale"] is None else p["scale"].contiguous()
+    sh = p["shift"].contiguous()
+    outs = []
+    for fill in (("nan", "zero") if c.twice else ("nan",)):
+        y = torch.full(yshape, float("nan"), dtype=torch.bfloat16 if cl_out else torch.float32, device=DEV)
+        scr = torch.full((max(need, 1),), float("nan") if fill == "nan" else 0.0, device=DEV)
+        rc = lib.s3r_conv_forward(C.byref(desc), xp.data_ptr(), pk.data_ptr(), sc.data_ptr() if sc is not None else None,
+                                  sh.data_ptr(), y.data_ptr(), scr.data_ptr(), need, None)
+        sync()
+        if c.refused:                                 # bf16: the forced tile is refused when the launch is resolved, before any kernel
+            assert rc < 0 and lib.s3r_last_error() and bool(torch.isnan(y).all()), (c.id, "expected to be refused", rc)
+            return None
+        rc_ok(lib, rc, c.id)
+        outs.append(interior(y, oh, sp, cl_out).contiguous())
+    if len(outs) == 2:
+        view = torch.int16 if cl_out else torch.int32
+        assert torch.equal(outs[0].view(view), outs[1].view(view)), "the result depends on the scratch contents"
+    return outs[0]
+
+
+def _check_conv(s3r, lib, c):
+    got = run_conv(s3r, lib, c)
+    if got is None:
+        return
+    x, p, want = _data(c.data)
+    assert_bits(got, want, c.data, p, c.id)
+
+
+# ---------------------------------------------------------------- direct fp32
+@pytest.mark.parametrize("case", X.DIRECT_CASES, ids=[c.id for c in X.DIRECT_CASES])
+def test_direct_fp32(s3r, lib, case):
+    _check_conv(s3r, lib, case)
+
+
+# ---------------------------------------------------------------- linear
+@pytest.mark.parametrize("case", X.LINEAR_CASES, ids=[c.id for c in X.LINEAR_CASES])
+def test_linear(s3r, lib, case):
+    l, B = case.layer, case.B
+    x, p, want = _data(case.data)
+    need = lib.s3r_linear_scratch_elems(B, l.cin, l.cout)
+    assert need >= 0, lib.s3r_last_error()
+    w, b = p["w"].contiguous(), p["shift"].contiguous()
+    outs = []
+    for fill in (("nan", "zero") if case.twice else ("nan",)):
+        y = torch.full((B, l.cout), float("nan"), device=DEV)
+        scr = torch.full((max(need, 1),), float("nan") if fill == "nan" else 0.0, device=DEV)
+        rc_ok(lib, lib.s3r_linear_forward(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), B, l.cin, l.cout, s3r._lib.ACT[l.act],
+                                          scr.data_ptr(), need, None), case.id)
+        sync()
+        outs.append(y)
+    if len(outs) == 2:
+        assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), "the result depends on the scratch contents"
+    assert_bits(outs[0], want, case.data, p, case.id)
+
+
+# ---------------------------------------------------------------- bf16
+@pytest.mark.parametrize("case", X.BF16_CASES, ids=[c.id for c in X.BF16_CASES])
+def test_bf16(s3r, lib, case, mfma_shape):
+    _check_conv(s3r, lib, case)
+
+
+# ---------------------------------------------------------------- Winograd fp32
+@pytest.mark.parametrize("case", X.WINO_CASES, ids=[c.id for c in X.WINO_CASES])
+def test_winograd_fp32(s3r, lib, case):
+    _check_conv(s3r, lib, case)
+
+
+# ---------------------------------------------------------------- producers that write a consumer's input
+@pytest.mark.parametrize("case", X.CV_CASES, ids=[c.id for c in X.CV_CASES])
+def test_cost_volume_planes_feed_v1(s3r, lib, case):
+    """the cost volume written as v1's transformed plane sets (never as a volume), v1 reading them through in_layout"""
+    l, B, D, H, W, Cc = case.data.layer, case.B, X.spec.MAX_DISP, X.spec.FEAT_HW, X.spec.FEAT_HW, X.spec.FEAT_C
+    vol, p = case.make()
+    vol = vol.to(DEV)
+    p = {k: None if v is None else v.to(DEV).contiguous() for k, v in p.items()}
+    want = LT.expected(l, vol, p)
+    fl, fr = (t.to(DEV).contiguous() for t in case.features())
+    if case.kind == "wino":
+        n, fn, layout = 6 * B * 2 * Cc * (D + 2) * (H // 4) * (W + 2), lib.s3r_cost_volume_forward_wino, s3r._lib.LAYOUT_WINO_H
+    else:
+        n, fn, layout = 36 * B * 2 * Cc * (D // 4) * (H // 4) * (W + 2), lib.s3r_cost_volume_forward_wino2, s3r._lib.LAYOUT_WINO_DH
+    planes = torch.zeros(n, device=DEV)                        # (the plane layouts are written into a zero-initialised buffer: include/s3r.h)
+    rc_ok(lib, fn(fl.data_ptr(), fr.data_ptr(), planes.data_ptr(), B, Cc, D, H, W, None), case.id)
+    desc = s3r._lib.make_desc(l, B, D, in_halo=1, algo=X.WINO, in_layout=layout)
+    need = lib.s3r_conv_scratch_elems(C.byref(desc))
+    assert need >= 0, lib.s3r_last_error()
+    npk = C.c_int64(0)
+    rc_ok(lib, lib.s3r_conv_packed_elems(C.byref(desc), C.byref(npk)), "packed_elems")
+    pk = torch.full((npk.value,), float("nan"), device=DEV)
+    rc_ok(lib, lib.s3r_conv_pack_weights(C.byref(desc), p["w"].data_ptr(), pk.data_ptr(), None), "pack_weights")
+    outs = []
+    for fill in ("nan", "zero"):
+        y = torch.full((B, l.cout, D, H, W), float("nan"), device=DEV)
+        scr = torch.full((max(need, 1),), float("nan") if fill == "nan" else 0.0, device=DEV)
+        rc_ok(lib, lib.s3r_conv_forward(C.byref(desc), planes.data_ptr(), pk.data_ptr(), p["scale"].data_ptr(), p["shift"].data_ptr(),
+                                        y.data_ptr(), scr.data_ptr(), need, None), case.id)
+        sync()
+        outs.append(y)
+    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), "the result depends on the scratch contents"
+    assert_bits(outs[0], want, case.data, p, case.id)
+
+
+CHAIN_RUNS = [(c, m) for c in X.CHAIN_CASES for m in ((32, 16) if c.dtype == "bf16" else (None,))]
+
+
+@pytest.mark.parametrize("case,mfma", CHAIN_RUNS, ids=[c.id + (f"-mfma{m}" if m else "") for c, m in CHAIN_RUNS])
+def test_chain_handoff(s3r, lib, case, mfma, monkeypatch):
+    """two layers through s3r_chain_forward: the stem writing e2's transformed planes; bf16 d3 with the head fused into its launch
+    (under both matrix instructions)"""
+    bf = case.dtype == "bf16"
+    if mfma:
+        monkeypatch.setenv("S3R_BF16_MFMA", str(mfma))
+    x, ps = case.make()
+    x = x.to(DEV)
+    ps = [{k: None if v is None else v.to(DEV).contiguous() for k, v in p.items()} for p in ps]
+    parts = (case.first, case.second)
+    want = LT.expected(case.second.layer, case.intermediate(x, ps[0]), ps[1])       # (both chains end in fp32)
+    B = case.first.B
+    arr = (s3r._lib.Layer * 2)()
+    keep = []
+    for i, (d, p) in enumerate(zip(parts, ps)):
+        desc = s3r._lib.make_desc(d.layer, B, d.n_in, tag=i, dtype=s3r._lib.DTYPE[case.dtype])
+        npk = C.c_int64(0)
+        rc_ok(lib, lib.s3r_conv_packed_elems(C.byref(desc), C.byref(npk)), "packed_elems")
+        pk = torch.full((npk.value,), float("nan"), device=DEV)
+        rc_ok(lib, lib.s3r_conv_pack_weights(C.byref(desc), p["w"].data_ptr(), pk.data_ptr(), None), "pack_weights")
+        arr[i].desc, arr[i].packed_w = desc, pk.data_ptr()
+        arr[i].scale = p["scale"].data_ptr() if p["scale"] is not None else None
+        arr[i].shift = p["shift"].data_ptr()
+        keep.append(pk)
+    need = lib.s3r_chain_workspace_elems(arr, 2)
+    assert need > 0, lib.s3r_last_error()
+    xin = x.to(torch.bfloat16).permute(0, *range(2, x.dim()), 1).contiguous() if bf else x.contiguous()
+    outs = []
+    s3r.profile_enable(16)
+    try:
+        for fill in ("nan", "zero"):
+            y = torch.full(want.shape, float("nan"), device=DEV)
+            ws = torch.full((need,), float("nan") if fill == "nan" else 0.0, device=DEV)
+            rc_ok(lib, lib.s3r_chain_forward(arr, 2, xin.data_ptr(), y.data_ptr(), ws.data_ptr(), need, 1, None), case.id)
+            sync()
+            outs.append(y)
+        rec = s3r.profile_read(16)
+    finally:
+        s3r.profile_enable(0)
+    assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), "the result depends on the workspace contents"
+    if bf:            # the hand-off under test is the one that ran: the head inside d3's launch; e2 on a Winograd form
+        assert not [r for r in rec if r["family"] == "head"] and [r for r in rec if r["family"] == "conv_mfma" and r["tag"] == 0], rec
+    else:
+        assert [r for r in rec if r["family"] == "conv_mfma" and r["tag"] == 1 and r["ran"].startswith("winograd")], rec
+    assert_bits(outs[0], want, case.second, ps[1], case.id)
+
+
+# ---------------------------------------------------------------- the instrument itself, on the device
+@pytest.mark.parametrize("case", [c for c in X.ALL_CASES if c.id in ("p1-B1", "linear-32x32768x1024-none", "v6-relu-B1", "wino2-tile3-v5")],
+                         ids=lambda c: c.id)
+def test_one_dropped_term_is_a_mismatch(s3r, lib, case, monkeypatch):
+    """ONE (channel, tap) weight zeroed in what the kernel is given: the output must differ from the untouched reference, and equal
+    the reference of the mutated weights bit for bit — at K = 32768 and 16384, below tests/_ref64.py's bound"""
+    x, p, want = _data(case.data)
+    w = p["w"]
+    t = int(w.reshape(-1).nonzero()[0, 0])
+    q = dict(p, w=w.clone())
+    q["w"].reshape(-1)[t] = 0.0
+    monkeypatch.setitem(_DATA, case.data, (x, q, LT.expected(case.layer, x, q)))
+    if case.layer.op == "linear":
+        y = torch.full((case.B, case.layer.cout), float("nan"), device=DEV)
+        need = lib.s3r_linear_scratch_elems(case.B, case.layer.cin, case.layer.cout)
+        scr = torch.full((max(need, 1),), float("nan"), device=DEV)
+        rc_ok(lib, lib.s3r_linear_forward(x.data_ptr(), q["w"].data_ptr(), q["shift"].data_ptr(), y.data_ptr(), case.B, case.layer.cin,
+                                          case.layer.cout, s3r._lib.ACT[case.layer.act], scr.data_ptr(), need, None), case.id)
+        sync()
+        got = y
+    else:
+        got = run_conv(s3r, lib, case)
+    assert not torch.equal(got.view(torch.int32), want.view(torch.int32)), "a dropped term went unseen"
+    assert_bits(got, _DATA[case.data][2], case.data, q, case.id)
