@@ -31,6 +31,15 @@
  *   - return value: S3R_OK (0) or a negative s3r_status; s3r_last_error() gives a message for the
  *     calling thread; nothing throws across the ABI;
  *   - every tensor of one call must be < 2^31 elements and < 4 GiB (32-bit buffer offsets);
+ *   - alignment: an fp32 or int32 tensor needs 4-byte alignment, at every entry point and for every argument (activations,
+ *     weights, packed weights, scale / shift / bias, scratch, workspaces, outputs, indices, counts), and the result does not depend
+ *     on the address: the same bits at a 4-byte-aligned pointer as at a 256-byte-aligned one (carving x, y, scratch and ws out of one
+ *     arena at float granularity is fine).  A bf16 tensor must be 16-byte aligned at every entry that takes or writes one, and so
+ *     must the scratch of an S3R_BF16 layer call and the workspace of a chain with S3R_BF16 layers (they hold bf16 intermediates);
+ *     channels-last with channels % 8 == 0 keeps every sample and pixel boundary 16-byte aligned.  Render tensors must be 16-byte
+ *     aligned, fp32 and 8-bit alike (the stems fetch whole render rows 16 bytes at a time).  A pointer that breaks one of these is
+ *     refused with S3R_ERR_INVALID and a message that contains "16-byte aligned", before anything is enqueued.  Nothing needs more:
+ *     not 128, not 256 bytes;
  *   - size queries (s3r_conv_scratch_elems, s3r_chain_workspace_elems, ...) do not depend on the device they are asked on: launch
  *     forms of one algorithm (bit-identical among themselves) are planned against the current device's compute-unit count and have
  *     different scratch footprints, so whenever the LIBRARY picks the form the query is sized for the largest one (r06).  A process
@@ -226,6 +235,7 @@ int s3r_chain_forward(const s3r_layer* layers, int n_layers, const void* x, void
  *            reference's forward receives them (README.md:73-74); the shared-weight tower runs once over all 2B
  *            images and the first kernel picks its source by image index, so nothing is concatenated.
  *            images_right = NULL: `images_left` holds all N images (any N).
+ *            images_left and images_right must be 16-byte aligned (also for s3r_chain_forward and s3r_conv_forward on the stem).
  *   decoder: cost volume (B,2C,D,H,W) -> occupancy (B,32,32,32)  */
 int s3r_encoder_forward(const s3r_layer* layers, int n_layers, const float* images_left, const float* images_right,
                         void* features, float* ws, int64_t ws_elems, int ws_fresh, void* stream);

@@ -11,6 +11,14 @@ using namespace s3rh;
 
 namespace {
 
+// bf16 tensors (channels-last activations, and the scratch / workspace that holds them) are read and written with 16-byte accesses
+// whose addresses are base + a multiple of 16 bytes: the base must be 16-byte aligned (include/s3r.h, Conventions).  fp32 and int32
+// tensors need their natural 4 bytes only.  Checked on the host, before anything is enqueued
+inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+int bf16_align_fail(const char* what, const void* p) {
+    return fail(S3R_ERR_INVALID, "%s must be 16-byte aligned (got %p): bf16 tensors are accessed 16 bytes at a time", what, p);
+}
+
 // input transform + class kernel + finish, in sub-batches that keep the transformed input inside 32-bit byte offsets
 int wino2_run(const s3r_conv_desc* d, const Geo& g, s3r::ConvParams p, const float* x, const float* packed_w, float* y, float* scratch,
               int64_t scratch_elems, int form, hipStream_t s, int* launches) {
@@ -309,7 +317,13 @@ int conv_forward_impl(const s3r_conv_desc* d, const void* xv, const void* x2v, i
     if (x2 && (nsplit <= 0 || nsplit >= d->batch)) return fail(S3R_ERR_INVALID, "split %d outside (0, batch=%d)", nsplit, d->batch);
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = hipSuccess;
+    // the stems fetch render rows by 16-byte vector loads / LDS-DMA from base + row * width (fp32 and 8-bit renders alike)
+    if (r == R_STEM && (misaligned16(xv) || misaligned16(x2v)))
+        return fail(S3R_ERR_INVALID, "render tensors must be 16-byte aligned (got %p, %p)", xv, x2v);
     if (d->dtype == S3R_BF16) {
+        if (r != R_STEM && misaligned16(xv)) return bf16_align_fail("the bf16 input of an S3R_BF16 layer", xv);
+        if (r != R_HEAD && misaligned16(yv)) return bf16_align_fail("the bf16 output of an S3R_BF16 layer", yv);
+        if (scratch && misaligned16(scratch)) return bf16_align_fail("the scratch of an S3R_BF16 layer", scratch);
         if (g.x_elems * 2 >= ((int64_t)1 << 31) || g.y_elems * 2 >= ((int64_t)1 << 31))
             return fail(S3R_ERR_INVALID, "bf16 path: tensors must be < 2 GiB per call: split the batch");
         switch (r) {
@@ -610,6 +624,15 @@ int chain_forward_impl(const s3r_layer* layers, int n_layers, const void* x, con
     int rc = plan_chain(layers, n_layers, &pl);
     if (rc) return rc;
     if (!x || !y) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    {   // bf16 hand-off points and the workspace that holds bf16 intermediates (the first layer's renders are checked below)
+        const int last = n_layers - 1;
+        bool any_bf16 = false;
+        for (int i = 0; i < n_layers; ++i) any_bf16 = any_bf16 || pl.d[i].dtype == S3R_BF16;
+        if (pl.d[0].dtype == S3R_BF16 && pl.r[0] != R_STEM && misaligned16(x)) return bf16_align_fail("the bf16 input of an S3R_BF16 chain", x);
+        if (pl.d[last].dtype == S3R_BF16 && pl.r[last] != R_HEAD && misaligned16(y))
+            return bf16_align_fail("the bf16 output of an S3R_BF16 chain", y);
+        if (any_bf16 && pl.total > 0 && ws && misaligned16(ws)) return bf16_align_fail("the workspace of a chain with S3R_BF16 layers", ws);
+    }
     if (pl.total > 0 && (!ws || ws_elems < pl.total))
         return fail(S3R_ERR_WORKSPACE, "chain needs a workspace of %lld floats, got %lld", (long long)pl.total,
                     (long long)ws_elems);
@@ -711,6 +734,7 @@ int s3r_encoder_forward_u8(const s3r_layer* layers, int n_layers, const uint8_t*
 
 int s3r_channels_last_to_f32(const void* x, float* y, int batch, int channels, int64_t positions, void* stream) {
     if (!x || !y) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    if (misaligned16(x)) return bf16_align_fail("the bf16 channels-last tensor", x);
     if (batch <= 0 || channels <= 0 || positions <= 0) return fail(S3R_ERR_INVALID, "dims must be positive");
     if (batch > 65535 || (int64_t)channels * positions >= kMaxElems)
         return fail(S3R_ERR_INVALID, "tensor too large for one call: split the batch");
@@ -790,6 +814,9 @@ int s3r_cost_volume_forward_wino2(const float* fl, const float* fr, float* plane
 int s3r_cost_volume_forward_bf16(const void* fl, const void* fr, void* vol, int batch, int channels, int max_disp,
                                  int height, int width, int out_halo, void* stream) {
     if (!fl || !fr || !vol) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    if (misaligned16(fl)) return bf16_align_fail("the left bf16 features", fl);
+    if (misaligned16(fr)) return bf16_align_fail("the right bf16 features", fr);
+    if (misaligned16(vol)) return bf16_align_fail("the bf16 cost volume", vol);
     if (batch <= 0 || channels <= 0 || max_disp <= 0 || height <= 0 || width <= 0)
         return fail(S3R_ERR_INVALID, "cost volume dims must be positive");
     if (channels % 8 != 0) return fail(S3R_ERR_INVALID, "bf16 cost volume needs channels %% 8 == 0");
@@ -892,6 +919,8 @@ int s3r_disparity_soft(const void* feat_l, const void* feat_r, int feat_dtype, f
     if (feat_dtype != S3R_F32 && feat_dtype != S3R_BF16) return fail(S3R_ERR_INVALID, "unknown feature dtype %d", feat_dtype);
     const bool bf16 = feat_dtype == S3R_BF16;
     if (bf16 && channels % 8 != 0) return fail(S3R_ERR_INVALID, "bf16 channels-last features need channels %% 8 == 0");
+    if (bf16 && batch > 0 && (((uintptr_t)feat_l | (uintptr_t)feat_r) & 15))
+        return fail(S3R_ERR_INVALID, "bf16 features must start 16-byte aligned (16-byte loads)");
     if (s3r::disparity_soft_lds_bytes(channels, max_disp, width) > 64 * 1024)
         return fail(S3R_ERR_INVALID, "soft read-out: 4*(2*C*W + 2*W*min(max_disp, W) + 12*W) bytes must fit 64 KiB of LDS");
     const int64_t feat = (int64_t)batch * channels * height * width;
@@ -901,8 +930,6 @@ int s3r_disparity_soft(const void* feat_l, const void* feat_r, int feat_dtype, f
         return fail(S3R_ERR_INVALID, "batch x out_height must stay below 2^24: split the batch");
     if (batch == 0) return S3R_OK;
     if (!feat_l || !feat_r) return fail(S3R_ERR_INVALID, "null feature pointer");
-    if (bf16 && (((uintptr_t)feat_l | (uintptr_t)feat_r) & 15))
-        return fail(S3R_ERR_INVALID, "bf16 features must start 16-byte aligned (16-byte loads)");
     hipStream_t s = (hipStream_t)stream;
     const int maps = !!disp_l + !!disp_r + !!conf_l + !!conf_r;
     ProfScope ps(s, F_DISP, 2, 0.0, (bf16 ? 2.0 : 4.0) * 2.0 * (double)feat + 4.0 * maps * (double)out);

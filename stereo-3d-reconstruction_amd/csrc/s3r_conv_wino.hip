@@ -1318,6 +1318,7 @@ __global__ __launch_bounds__(256) void wino2p_input_kernel(const float* __restri
 // the same transform with the planes staged in LDS: a workgroup owns one channel of NS samples (NS x SH x SW <= 256 groups), loads
 // their padded planes with 16-byte accesses and reads the 6 x 6 windows from LDS (the flat kernel's 36 loads per thread are 16 bytes
 // apart between lanes: 3.2 TB/s); same operations per value, same bits
+typedef float wv4f_u __attribute__((ext_vector_type(4), aligned(4)));      // a 16-byte global access at a dword-aligned address
 __global__ __launch_bounds__(256) void wino2p_input_lds_kernel(const float* __restrict__ x, float* __restrict__ V, int B, int Cin, int Hp,
                                                                int Wp, int SH, int SW, int NS, unsigned npad) {
     extern __shared__ __attribute__((aligned(16))) float w2p_sx[];
@@ -1330,7 +1331,7 @@ __global__ __launch_bounds__(256) void wino2p_input_lds_kernel(const float* __re
         float* dstp = w2p_sx + sidx * plane;
         if ((plane & 3) == 0) {
             for (int i = threadIdx.x; i < plane / 4; i += 256)
-                reinterpret_cast<float4*>(dstp)[i] = reinterpret_cast<const float4*>(src)[i];
+                reinterpret_cast<wv4f*>(dstp)[i] = reinterpret_cast<const wv4f_u*>(src)[i];      // (x: 4-byte alignment only)
         } else {
             for (int i = threadIdx.x; i < plane; i += 256) dstp[i] = src[i];
         }

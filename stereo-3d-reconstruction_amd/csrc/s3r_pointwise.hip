@@ -489,7 +489,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
     v4f acc = {0.f, 0.f, 0.f, 0.f};
     const float sc = scale ? scale[0] : 1.f, sf = shift ? shift[0] : 0.f;
     for (int c = 0; c < C; ++c) {
-        const v4f v = *reinterpret_cast<const v4f*>(xb + (size_t)c * S);
+        const v4f v = *reinterpret_cast<const v4f_u*>(xb + (size_t)c * S);      // (x and y need 4-byte alignment only)
         const float wc = w[c];
         acc[0] = fmaf(v[0], wc, acc[0]);
         acc[1] = fmaf(v[1], wc, acc[1]);
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ x, 
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) acc[k] = apply_act(fmaf(acc[k], sc, sf), act);
-    *reinterpret_cast<v4f*>(y + (size_t)b * S + sp) = acc;
+    *reinterpret_cast<v4f_u*>(y + (size_t)b * S + sp) = acc;
 }
 
 hipError_t launch_head(const float* x, const float* w, const float* scale, const float* shift, float* y, int B, int C,

@@ -61,6 +61,13 @@ class debug_overrides:
         return {k: dict(v) for k, v in _DEBUG.items() if v}
 
 
+def _aligned16(x: torch.Tensor) -> torch.Tensor:
+    """The library's alignment contract (include/s3r.h, Conventions) for the tensors that need more than their element size: a
+    bf16 tensor and a render must start 16-byte aligned.  A torch view at a storage offset that breaks it (a slice of a larger
+    buffer) is copied once, so that no view is ever refused; fp32 / int32 tensors need 4 bytes and never come here."""
+    return x.clone() if x.data_ptr() % 16 else x
+
+
 def _to_channels_last_physical(x: torch.Tensor) -> torch.Tensor:
     """logical (B,C,...) tensor -> contiguous physical (B,...,C) tensor (no copy if already channels-last)."""
     nd = x.dim()
@@ -81,7 +88,7 @@ def _check_input_cl(x: torch.Tensor, name: str, shape_tail: Sequence[int], dtype
         raise RuntimeError(f"{name} must have shape (B, {', '.join(map(str, shape_tail))}), got {tuple(x.shape)}")
     nd = x.dim()
     phys = x.permute(0, *range(2, nd), 1)
-    return phys if phys.is_contiguous() else phys.contiguous()
+    return _aligned16(phys if phys.is_contiguous() else phys.contiguous())
 
 
 def _to_logical(x: torch.Tensor) -> torch.Tensor:
@@ -103,17 +110,16 @@ def _check_input(x: torch.Tensor, name: str, shape_tail: Sequence[int], dtype=to
         raise RuntimeError(f"{name} must be {dtype} (got {x.dtype})")
     if tuple(x.shape[1:]) != tuple(shape_tail):
         raise RuntimeError(f"{name} must have shape (B, {', '.join(map(str, shape_tail))}), got {tuple(x.shape)}")
-    return x.contiguous()
+    x = x.contiguous()
+    return _aligned16(x) if dtype == torch.bfloat16 else x      # (fp32 / 8-bit: the storage offset is kept; renders: _check_render)
 
 
 def _check_render(x: torch.Tensor, name: str) -> torch.Tensor:
     """A batch of renders, (B,3,224,224): float32 in [0,1], or uint8 as a PNG decode yields them (the stem scales by
     1/255 as it reads, bit-identical to `x.float() / 255` on the host: `s3r_encoder_forward_u8`)."""
     dt = x.dtype if isinstance(x, torch.Tensor) and x.dtype == torch.uint8 else torch.float32
-    x = _check_input(x, name, (3, spec.IMG_HW, spec.IMG_HW), dt)
-    if x.data_ptr() % 16:           # the stems fetch whole rows by 16-byte LDS-DMA: a view at an odd storage offset is copied once
-        x = x.clone()
-    return x
+    # the stems fetch whole rows by 16-byte LDS-DMA: a view at an odd storage offset is copied once
+    return _aligned16(_check_input(x, name, (3, spec.IMG_HW, spec.IMG_HW), dt))
 
 
 @torch.no_grad()
@@ -912,8 +918,7 @@ def disparity_soft(feat_l: torch.Tensor, feat_r: torch.Tensor, max_disp: int = s
     bf16 = feat_l.dtype == torch.bfloat16
     chk = _check_input_cl if bf16 else _check_input
     pl, pr = chk(feat_l, "feat_l", feat_l.shape[1:], feat_l.dtype), chk(feat_r, "feat_r", feat_r.shape[1:], feat_r.dtype)
-    if bf16:                        # the kernel reads bf16 rows in 16-byte pieces: a view at an odd storage offset is copied once
-        pl, pr = (p if p.data_ptr() % 16 == 0 else p.clone() for p in (pl, pr))
+    # (bf16: the kernel reads rows in 16-byte pieces; _check_input_cl copies a view at an odd storage offset once)
     B, Cc, H, W = feat_l.shape
     OH, OW = (H, W) if out_size is None else (int(out_size[0]), int(out_size[1]))
     dev = feat_l.device

@@ -2,7 +2,9 @@
 
 Every argument of a call gets ONE allocation laid out as [front guard | payload | back guard].  Each guard is GUARD_BYTES (16 KiB:
 wider than one tile row of any kernel, so a wrong stride lands inside it) and the payload starts 256-byte aligned (the alignment the
-stem checks).  Everything a kernel could write lands inside the one allocation: a stray write is DATA here, never a fault.
+stem checks) unless the argument is given a `skew`: the payload then starts `skew` ELEMENTS past a 256-byte boundary, the guards
+still contiguous around it (tests/test_alignment_gpu.py: "at which address").  Everything a kernel could write lands inside the one
+allocation: a stray write is DATA here, never a fault.
 
 The payload is filled by the argument's role, and check() compares bit patterns, not values:
 
@@ -18,10 +20,15 @@ Guards hold GUARD (fp32 0x7FA5A5A5 / bf16 0x7FA5: signalling-NaN payloads no ker
 and poison are the same bit pattern (two's complement): both are negative, and every int32 output of the library (indices,
 counts) is >= 0, so neither can be a legitimate value.
 
+Skews are given per argument (`skew=`), or by argument name for a whole test body: `with skews({"x": 1, "y": 3}):` or
+`with skews(lambda name, dtype, role: ...)` — every Guarded built inside takes its skew from there unless it passes one itself.
+
 check() returns None or the FIRST offending place, e.g. "back guard of scratch +1344" (element offset from the start of that
 region) or "leftover poison in y +17 (index (0, 1, 2, 3))".
 """
 from __future__ import annotations
+
+import contextlib
 
 import torch
 
@@ -54,10 +61,31 @@ def interior_mask(shape, halo, spatial):
     return m
 
 
+_SKEWS = [None]          # the innermost `with skews(...)`: a dict name -> elements, or a callable (name, dtype, role) -> elements
+
+
+@contextlib.contextmanager
+def skews(by_name):
+    """every Guarded built in the body that passes no skew of its own takes `by_name[name]` (a dict; a missing name is 0) or
+    `by_name(name, dtype, role)` (a callable) elements"""
+    _SKEWS.append(by_name)
+    try:
+        yield
+    finally:
+        _SKEWS.pop()
+
+
+def _skew_of(name, dtype, role):
+    s = _SKEWS[-1]
+    if s is None:
+        return 0
+    return int(s(name, dtype, role) if callable(s) else s.get(name, 0))
+
+
 class Guarded:
     """One argument of a call.  `.t` is the payload (a view of `shape`), `.ptr` its device address."""
 
-    def __init__(self, name, shape, dtype, device, role, data=None, halo=0, spatial=(), fill="nan", mask=None, halo_zeros=False):
+    def __init__(self, name, shape, dtype, device, role, data=None, halo=0, spatial=(), fill="nan", mask=None, halo_zeros=False, skew=None):
         if isinstance(shape, int):
             shape = (shape,)
         self.name, self.shape, self.dtype, self.role = name, tuple(shape), dtype, role
@@ -67,14 +95,17 @@ class Guarded:
         for s in self.shape:
             n *= s
         self.n = n
-        base = torch.empty(2 * self.g + n + ALIGN // esz, dtype=dtype, device=device)
-        lead = (-base.data_ptr()) % ALIGN // esz                 # (the device allocator aligns already; the host one may not)
+        self.skew = _skew_of(name, dtype, role) if skew is None else int(skew)
+        assert self.skew >= 0
+        base = torch.empty(2 * self.g + n + self.skew + ALIGN // esz, dtype=dtype, device=device)
+        lead = (-base.data_ptr()) % ALIGN // esz + self.skew     # (the device allocator aligns already; the host one may not)
         self.raw = base[lead:lead + 2 * self.g + n]
         bits = _as_bits(self.raw)
         bits.fill_(_BITS[dtype][1])
         self.t = self.raw[self.g:self.g + n].view(self.shape)
-        assert self.raw.data_ptr() % ALIGN == 0 and self.t.data_ptr() % ALIGN == 0, "payload must start 256-byte aligned"
-        self.ptr = self.t.data_ptr()
+        self.ptr = self.raw.data_ptr() + GUARD_BYTES             # (an empty payload has no address of its own)
+        assert (self.ptr - self.skew * esz) % ALIGN == 0 and (n == 0 or self.t.data_ptr() == self.ptr), \
+            "payload must start skew elements past a 256-byte aligned address (skew 0: 256-byte aligned), guards contiguous around it"
         self.mask = None
         self.halo_zeros = halo_zeros          # the kernel may rewrite the halo with +0.0 (the zeros the contract says it holds)
         if role == "in":

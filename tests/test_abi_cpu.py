@@ -235,6 +235,113 @@ def test_every_entry_that_reaches_a_stem_checks_render_alignment(s3r, lib):
         assert b"16-byte aligned" in lib.s3r_last_error(), lib.s3r_last_error()
 
 
+def _bf16_refusal_calls(s3r, lib):
+    """(id, call(ptrs) -> rc, names of the bf16 pointers, names of the fp32 pointers, the message of the LATER host check every call
+    here is built to run into — a workspace of 0 floats, a shape the entry refuses — so that nothing is ever launched)"""
+    spec, Ld = s3r.arch_spec, s3r._lib
+    BF = Ld.DTYPE["bf16"]
+    net = dict((l.name, (l, n)) for stage in ("encoder", "decoder") for l, n, _ in spec.stage_table(stage))
+    # one layer, forced split-K, scratch_elems = 0: S3R_ERR_WORKSPACE after every alignment check
+    conv = Ld.make_desc(spec.Layer("t", "conv3d", 64, 40, 4, 1, 0), 2, 7, ksplit=2, dtype=BF)
+    head = Ld.make_desc(spec.Layer("t", "conv3d", 64, 40, 4, 1, 0), 2, 7, ksplit=2, dtype=0)
+
+    def layers(rows, batch, dtype):
+        arr = (Ld.Layer * len(rows))()
+        for i, (l, n, _) in enumerate(rows):
+            arr[i].desc = Ld.make_desc(l, batch, n, dtype=dtype)
+        return arr, len(rows)
+
+    enc, dec = layers(spec.stage_table("encoder"), 2, BF), layers(spec.stage_table("decoder"), 1, BF)
+    two = layers(spec.stage_table("decoder")[:2], 1, BF)
+    return [
+        ("conv_forward-bf16", lambda p, d=conv: lib.s3r_conv_forward(C.byref(d), p["x"], p["packed"], p["scale"], p["shift"], p["y"],
+                                                                     p["scratch"], 0, None),
+         ("x", "y", "scratch"), ("packed", "scale", "shift"), b"needs"),
+        ("conv_forward-fp32", lambda p, d=head: lib.s3r_conv_forward(C.byref(d), p["x"], p["packed"], p["scale"], p["shift"], p["y"],
+                                                                     p["scratch"], 0, None),
+         (), ("x", "y", "scratch", "packed", "scale", "shift"), b"needs"),
+        ("chain_forward", lambda p: lib.s3r_chain_forward(*two, p["x"], p["y"], p["ws"], 0, 1, None), ("x", "y", "ws"), (), b"workspace"),
+        ("encoder_forward", lambda p: lib.s3r_encoder_forward(*enc, p["left"], p["right"], p["features"], p["ws"], 0, 1, None),
+         ("features", "ws"), (), b"workspace"),
+        ("encoder_forward_u8", lambda p: lib.s3r_encoder_forward_u8(*enc, p["left"], p["right"], p["features"], p["ws"], 0, 1, None),
+         ("features", "ws"), (), b"workspace"),
+        # (the occupancy comes out of the fused head: fp32)
+        ("decoder_forward", lambda p: lib.s3r_decoder_forward(*dec, p["volume"], p["occupancy"], p["ws"], 0, 1, None),
+         ("volume", "ws"), ("occupancy",), b"workspace"),
+        ("cost_volume_forward_bf16", lambda p: lib.s3r_cost_volume_forward_bf16(p["left"], p["right"], p["volume"], 1, 4, 4, 4, 4, 0, None),
+         ("left", "right", "volume"), (), b"channels % 8"),
+        ("channels_last_to_f32", lambda p: lib.s3r_channels_last_to_f32(p["x"], p["y"], 70000, 8, 4, None), ("x",), ("y",), b"too large"),
+        ("disparity_soft-bf16", lambda p: lib.s3r_disparity_soft(p["left"], p["right"], BF, p["disp_l"], p["disp_r"], p["conf_l"], p["conf_r"],
+                                                                 1, 64, 4, 4096, 64, 1.0, 4, 4096, 1.0, None),
+         ("left", "right"), ("disp_l", "disp_r", "conf_l", "conf_r"), b"64 KiB"),
+        ("disparity_soft-fp32", lambda p: lib.s3r_disparity_soft(p["left"], p["right"], 0, p["disp_l"], p["disp_r"], p["conf_l"], p["conf_r"],
+                                                                 1, 64, 4, 4096, 64, 1.0, 4, 4096, 1.0, None),
+         (), ("left", "right", "disp_l", "disp_r", "conf_l", "conf_r"), b"64 KiB"),
+    ]
+
+
+ALL_POINTERS = ("x", "y", "scratch", "packed", "scale", "shift", "ws", "left", "right", "features", "volume", "occupancy", "disp_l",
+                "disp_r", "conf_l", "conf_r")
+
+
+def test_every_entry_that_takes_a_bf16_tensor_checks_its_alignment(s3r, lib):
+    """include/s3r.h, Conventions: a bf16 tensor (and the scratch / workspace of S3R_BF16 layers, which holds bf16 intermediates)
+    must be 16-byte aligned; fp32 / int32 tensors need 4 bytes.  Fake pointers, argument validation only: at addresses = 2, 4, 8
+    (mod 16) every bf16 pointer is refused with S3R_ERR_INVALID and "16-byte aligned" before the later host check the call is built
+    to fail (so nothing is launched, on any machine); at = 0 the call gets past the alignment check and meets that later one; an
+    fp32 pointer of the same entries at the same addresses is never refused for its alignment"""
+    base = 1 << 20
+    for name, call, bf16_ptrs, f32_ptrs, later in _bf16_refusal_calls(s3r, lib):
+        aligned = {k: C.c_void_p(base + 4096 * i) for i, k in enumerate(ALL_POINTERS)}
+        rc = call(aligned)
+        assert rc < 0 and later in lib.s3r_last_error() and b"16-byte aligned" not in lib.s3r_last_error(), (name, rc, lib.s3r_last_error())
+        for off in (2, 4, 8):
+            for k in bf16_ptrs:
+                p = dict(aligned)
+                p[k] = C.c_void_p(aligned[k].value + off)
+                assert call(p) == -1, (name, k, off)
+                assert b"16-byte aligned" in lib.s3r_last_error(), (name, k, off, lib.s3r_last_error())
+            for k in f32_ptrs:
+                if off == 2:
+                    continue                                     # (not an address an fp32 tensor can have)
+                p = dict(aligned)
+                p[k] = C.c_void_p(aligned[k].value + off)
+                rc = call(p)
+                assert rc < 0 and later in lib.s3r_last_error() and b"16-byte aligned" not in lib.s3r_last_error(), \
+                    (name, k, off, rc, lib.s3r_last_error())
+
+
+def test_alignment_exceptions_are_the_header_s_sentences(s3r):
+    """the (entry, argument) pairs whose fp32 / int32 / 8-bit pointer needs more than its element size: ONE table
+    (tests/_alignment_cases.py), every row quoting the sentence of include/s3r.h that documents it"""
+    from tests import _alignment_cases as AC
+    header = " ".join(re.sub(r"[/*]+", " ", open(os.path.join(ROOT, "include", "s3r.h")).read()).split())
+    assert AC.EXCEPTIONS
+    for entry, arg, name, nbytes, sentence, reason in AC.EXCEPTIONS:
+        assert " ".join(sentence.split()) in header, (entry, arg, sentence)
+        assert reason and name and nbytes == 16
+        assert entry in s3r._lib.SIGNATURES, entry
+
+
+def test_render_pointers_are_refused_at_every_entry_that_reaches_a_stem(s3r, lib):
+    """the exception list's rows, asserted: s3r_conv_forward on the stem descriptor (both precisions) refuses a render pointer that
+    is 4- or 8-byte aligned, like the chain and encoder entries above; its fp32 arguments are not refused for alignment"""
+    spec = s3r.arch_spec
+    l, n, _ = spec.stage_table("encoder")[0]
+    for dtype in (0, 1):
+        d = s3r._lib.make_desc(l, 2, n, dtype=dtype)
+        ok = C.c_void_p(1 << 20)
+        for off in (4, 8) + ((2,) if dtype else ()):
+            assert lib.s3r_conv_forward(C.byref(d), C.c_void_p(ok.value + off), ok, ok, ok, ok, None, 0, None) == -1
+            assert b"render tensors must be 16-byte aligned" in lib.s3r_last_error()
+        if dtype:
+            assert lib.s3r_conv_forward(C.byref(d), ok, ok, ok, ok, C.c_void_p(ok.value + 8), None, 0, None) == -1
+            assert b"16-byte aligned" in lib.s3r_last_error() and b"render" not in lib.s3r_last_error()
+        # (scale = NULL: "stem needs scale and shift" is the later host check)
+        assert lib.s3r_conv_forward(C.byref(d), ok, C.c_void_p(ok.value + 4), None, C.c_void_p(ok.value + 4), ok, None, 0, None) == -1
+        assert b"16-byte aligned" not in lib.s3r_last_error() and b"scale and shift" in lib.s3r_last_error()
+
+
 def test_missing_library_fails_loudly(s3r, monkeypatch, tmp_path):
     monkeypatch.setattr(s3r._lib, "_lib", None)
     monkeypatch.setattr(s3r._lib, "LIB_PATH", str(tmp_path / "nope.so"))

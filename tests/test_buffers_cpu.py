@@ -8,6 +8,7 @@ import os
 import pytest
 import torch
 
+from tests import _alignment_cases as AC
 from tests import _buffer_cases as BC
 from tests import _guard as G
 from tests import _ref64 as R
@@ -65,6 +66,77 @@ def test_guard_inputs_and_scratch():
     assert s.check() == f"back guard of scratch +{s.g - 1}"
     z = G.Guarded("ws", 0, torch.float32, "cpu", "scratch", fill="zero")
     assert z.check() is None and z.t.numel() == 0
+
+
+@pytest.mark.parametrize("skew", [1, 33])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.int32])
+def test_guard_at_a_skewed_payload(dtype, skew):
+    """a payload `skew` elements past a 256-byte boundary: guards, poison, sentinel and first-offender reporting as at skew 0"""
+    def out():
+        return G.Guarded("y", (2, 3, 6, 6), dtype, "cpu", "out", halo=1, spatial=(2, 3), skew=skew)
+
+    b = out()
+    esz = b.t.element_size()
+    assert b.skew == skew and b.t.data_ptr() % 256 == skew * esz % 256 and b.ptr == b.t.data_ptr()
+    assert b.t.data_ptr() - b.raw.data_ptr() == G.GUARD_BYTES and b.raw.numel() == 2 * b.g + b.n      # guards contiguous around it
+    assert b.check() == "leftover poison in y +7 (index (0, 0, 1, 1))"
+    b.t[:, :, 1:5, 1:5] = 1
+    assert b.check() is None
+    b.t[1, 2, 5, 0] = 0
+    assert b.check() == f"write into the halo of y +{36 * 5 + 30} (index (1, 2, 5, 0))"
+    b = out()
+    b.t[:, :, 1:5, 1:5] = 1
+    b.raw[b.g - 1] = 0                                           # a 16-byte store that starts one element early
+    assert b.check() == f"front guard of y +{b.g - 1}"
+    b = out()
+    b.t[:, :, 1:5, 1:5] = 1
+    b.raw[b.g + b.n] = 0                                         # ... or runs one element past the payload
+    assert b.check() == "back guard of y +0"
+    x = torch.arange(24, dtype=torch.float32).to(dtype).reshape(2, 12)
+    i = G.Guarded("x", x.shape, dtype, "cpu", "in", data=x, skew=skew)
+    assert i.check() is None and torch.equal(i.t, x)
+    i.t[1, 3] = 0
+    assert i.check() == "change of the input x +15 (index (1, 3))"
+    s = G.Guarded("scratch", 100, dtype, "cpu", "scratch", skew=skew) if dtype != torch.int32 else None
+    if s is not None:
+        assert torch.isnan(s.t.float()).all() and s.check() is None
+        s.raw[0] = 1.0
+        assert s.check() == "front guard of scratch +0"
+
+
+def test_skews_by_argument_name():
+    """`with G.skews(...)`: by dict or by callable; an explicit skew= wins; outside the block everything is aligned again"""
+    with G.skews({"x": 1, "ws": 33}):
+        x = G.Guarded("x", 8, torch.float32, "cpu", "scratch")
+        y = G.Guarded("y", 8, torch.float32, "cpu", "scratch")
+        ws = G.Guarded("ws", 8, torch.float32, "cpu", "scratch")
+        z = G.Guarded("x", 8, torch.float32, "cpu", "scratch", skew=0)
+        with G.skews(lambda name, dtype, role: 8 if dtype == torch.bfloat16 else 3):
+            h = G.Guarded("x", 8, torch.bfloat16, "cpu", "scratch")
+            f = G.Guarded("q", 8, torch.float32, "cpu", "scratch")
+        again = G.Guarded("x", 8, torch.float32, "cpu", "scratch")
+    after = G.Guarded("x", 8, torch.float32, "cpu", "scratch")
+    assert [b.ptr % 256 for b in (x, y, ws, z, h, f, again, after)] == [4, 0, 132, 0, 16, 12, 4, 0]
+    assert all(b.check() is None for b in (x, y, ws, z, h, f, again, after))
+
+
+def test_patterns_move_what_they_say():
+    """the pattern table of tests/test_alignment_gpu.py (tests/_alignment_cases.py): fp32 skews in elements, bf16 / render / bf16-workspace arguments at 16 or 144 bytes"""
+    f32, bf, u8 = torch.float32, torch.bfloat16, torch.uint8
+    p = AC.Pattern("mixed")
+    assert [p(n, f32, r) for n, r in (("x", "in"), ("w", "in"), ("packed", "out"), ("y", "out"), ("scratch", "scratch"), ("x", "in"))] == \
+        [1, 2, 3, 4, 33, 1]
+    for pid, want in (("all1", (1, 1, 1)), ("all3", (3, 3, 3)), ("in1", (1, 0, 0)), ("out1", (0, 1, 0)), ("out4", (0, 4, 0)), ("ws1", (0, 0, 1))):
+        p = AC.Pattern(pid)
+        assert tuple(p(n, f32, r) for n, r in (("x", "in"), ("y", "out"), ("ws", "scratch"))) == want, pid
+    p = AC.Pattern("all1", sixteen={"left"}, bf16_call=True)
+    assert (p("left", f32, "in"), p("left", u8, "in"), p("features", bf, "out"), p("ws", f32, "scratch"), p("packed0", f32, "out"),
+            p("shift", f32, "in")) == (4, 16, 8, 4, 1, 1)
+    p = AC.Pattern("all3", sixteen={"left"}, bf16_call=True)
+    assert (p("left", f32, "in"), p("left", u8, "in"), p("features", bf, "out"), p("ws", f32, "scratch")) == (36, 144, 72, 36)
+    with G.skews(AC.Pattern("all3", bf16_call=True)):
+        b = [G.Guarded(n, 8, dt, "cpu", role) for n, dt, role in (("x", bf, "scratch"), ("scratch", f32, "scratch"), ("shift", f32, "scratch"))]
+    assert [t.ptr % 256 for t in b] == [144, 144, 12] and [t.ptr % 16 for t in b[:2]] == [0, 0]
 
 
 # ---------------------------------------------------------------- the checker's mutation self-test

@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests import _abi_bodies as AB
 from tests import _disp64 as R
 from tests import _guard as G
 
@@ -152,33 +153,7 @@ GUARDED = [("fp32-upsample", F32, (2, 32, 28, 28, 28), (224, 224), True), ("fp32
 
 @pytest.mark.parametrize("case", GUARDED, ids=[c[0] for c in GUARDED])
 def test_guarded_buffers(s3r, lib, case):
-    _, dt, shape, (OH, OW), conf = case
-    B, Cc, H, W, D = shape
-    fl, fr = (t.to(DEV) for t in _feats(shape, 23 + sum(shape)))
-    if dt == BF16:
-        fl, fr = _cl_bf16(fl), _cl_bf16(fr)
-        phys = [x.permute(0, 2, 3, 1) for x in (fl, fr)]
-        a = G.Guarded("left", phys[0].shape, torch.bfloat16, DEV, "in", data=phys[0])
-        b = G.Guarded("right", phys[1].shape, torch.bfloat16, DEV, "in", data=phys[1])
-    else:
-        a = G.Guarded("left", fl.shape, torch.float32, DEV, "in", data=fl)
-        b = G.Guarded("right", fr.shape, torch.float32, DEV, "in", data=fr)
-    outs = [G.Guarded(n, (B, OH, OW), torch.float32, DEV, "out") for n in ("disp_l", "disp_r")]
-    if conf:
-        outs += [G.Guarded(n, (B, OH, OW), torch.float32, DEV, "out") for n in ("conf_l", "conf_r")]
-        cptr = [outs[2].ptr, outs[3].ptr]
-    else:                     # NULL confidence: buffers beside the call that nothing may touch
-        outs += [G.Guarded(n, (B, OH, OW), torch.float32, DEV, "in", data=torch.full((B, OH, OW), 7.0, device=DEV))
-                 for n in ("conf_l", "conf_r")]
-        cptr = [None, None]
-    rc = lib.s3r_disparity_soft(a.ptr, b.ptr, dt, outs[0].ptr, outs[1].ptr, cptr[0], cptr[1], B, Cc, H, W, D, 0.7, OH, OW,
-                                8.0, None)
-    assert rc == 0, lib.s3r_last_error().decode()
-    torch.cuda.synchronize()
-    G.check_all(a, b, *outs)
-    want = s3r.disparity_soft(fl, fr, D, 0.7, out_size=(OH, OW), scale=8.0, confidence=True)
-    for o, w in zip(outs[:4 if conf else 2], want):
-        assert torch.equal(o.t, w)
+    AB.disparity_soft(s3r, lib, case)
 
 
 def test_batch_zero_launches_nothing(s3r, lib):
