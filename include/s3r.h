@@ -16,6 +16,8 @@
  *   s3r_linear_forward                      the point decoder's nn.Linear layers        (README.md:36)
  *   s3r_chamfer_forward                     extensions/chamfer_dist (the reference's one native op,
  *                                           built by `python setup.py install`)         (README.md:64-65)
+ *   s3r_chamfer_backward                    the backward half of the same extension: the op is usable as a LOSS, with a fixed
+ *                                           summation order instead of the usual atomicAdd scatter   (README.md:64-65)
  *   s3r_voxel_iou                           the IoU metric of `runner.py --test`        (README.md:88-92)
  *   s3r_disparity_wta, s3r_disparity_epe    predicted left / right disparity and its end-point error
  *                                           against the disp_%02d_{l,r}.exr ground truth (README.md:75-76)
@@ -59,7 +61,7 @@ extern "C" {
  * fp32 layers; `tile` = 6 under S3R_ALGO_WINOGRAD names the three-axis form of a transposed convolution (AUTO takes it from edge
  * 16 up: other bits than ABI 7 for such a layer); s3r_profile_detail and record family 10 (aux passes).
  * s3r_disparity_soft and s3r_disparity_metrics were added later as new entry points only (no struct or existing signature changed):
- * the version stays 8. */
+ * the version stays 8.  s3r_chamfer_backward likewise. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -288,6 +290,27 @@ int s3r_linear_forward(const float* x, const float* w, const float* bias, float*
 /* squared-L2 nearest neighbours both ways; p (B,N,3), q (B,M,3) */
 int s3r_chamfer_forward(const float* p, const float* q, float* dist1, float* dist2, int32_t* idx1, int32_t* idx2,
                         int batch, int n, int m, void* stream);
+
+/* Backward of s3r_chamfer_forward: the gradient of sum_i grad_dist1[i] dist1[i] + sum_j grad_dist2[j] dist2[j] with respect to p and
+ * q, the indices held fixed.  p (B,N,3), q (B,M,3); idx1 (B,N) into q and idx2 (B,M) into p as s3r_chamfer_forward wrote them;
+ * grad_dist1 (B,N), grad_dist2 (B,M); grad_p (B,N,3), grad_q (B,M,3).  Per sample, with a_i = 2 grad_dist1[i] and c_j = 2 grad_dist2[j]
+ * (both exact in fp32), per component x, y, z:
+ *   grad_p[i] = a_i (p_i - q_idx1[i])  +  sum_{j ascending, idx2[j] == i}  c_j (p_i - q_j)
+ *   grad_q[j] = c_j (q_j - p_idx2[j])  +  sum_{i ascending, idx1[i] == j}  a_i (q_j - p_i)
+ * All arithmetic is fp32 without fused multiply-adds: the difference is rounded, then the product; the accumulator starts as the own
+ * term and the scattered terms are added one at a time in ascending source index.  This fixed order IS the contract: a gather, no
+ * atomics, no scratch — the same bits on every run, for every batch split, launch geometry and address (the usual atomicAdd scatter
+ * depends on arrival order).  NaN / Inf in the inputs propagate through exactly this arithmetic.
+ * grad_dist1 or grad_dist2 may be NULL: all zeros, the same bits as a zero tensor; both NULL is S3R_ERR_INVALID.  grad_p or grad_q
+ * may be NULL: that direction is not computed (a ground-truth cloud needs no gradient); both NULL is S3R_ERR_INVALID.  Otherwise
+ * validated as the forward: p, q, idx1, idx2 non-NULL, batch, n, m > 0, batch <= 65535, every tensor < 2^31 elements; 4-byte
+ * alignment for every argument.  Indices are trusted to be in range; the own-term index is still clamped to [0, m-1] / [0, n-1], so a
+ * garbage index never reads outside the clouds, and an out-of-range index matches no target in the scan.  One kernel launch, both
+ * directions and all samples.  Profiler: family 5, tag 1; `bytes` = the tensors it must read and write; `flops`, per computed
+ * direction, = 7 per target (one doubling, 3 differences, 3 products) + 10 per source (one doubling, 3 differences, 3 products, 3 adds):
+ * batch (7 n + 10 m) for grad_p, batch (7 m + 10 n) for grad_q — the index compares of the scan are not counted. */
+int s3r_chamfer_backward(const float* p, const float* q, const int32_t* idx1, const int32_t* idx2, const float* grad_dist1,
+                         const float* grad_dist2, float* grad_p, float* grad_q, int batch, int n, int m, void* stream);
 
 /* per-sample IoU of (pred > th) vs (gt > th) over `voxels` elements */
 int s3r_voxel_iou(const float* pred, const float* gt, float threshold, float* iou, int batch, int64_t voxels,

@@ -867,6 +867,27 @@ int s3r_chamfer_forward(const float* p, const float* q, float* dist1, float* dis
     return S3R_OK;
 }
 
+int s3r_chamfer_backward(const float* p, const float* q, const int32_t* idx1, const int32_t* idx2, const float* grad_dist1,
+                         const float* grad_dist2, float* grad_p, float* grad_q, int batch, int n, int m, void* stream) {
+    if (!p || !q || !idx1 || !idx2) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    if (!grad_dist1 && !grad_dist2) return fail(S3R_ERR_INVALID, "chamfer backward: grad_dist1 and grad_dist2 are both NULL (one may be: it means zeros)");
+    if (!grad_p && !grad_q) return fail(S3R_ERR_INVALID, "chamfer backward: grad_p and grad_q are both NULL (one may be: it is not computed)");
+    if (batch <= 0 || n <= 0 || m <= 0) return fail(S3R_ERR_INVALID, "chamfer needs non-empty clouds (batch=%d n=%d m=%d)", batch, n, m);
+    if (batch > 65535) return fail(S3R_ERR_INVALID, "batch > 65535: split the call");
+    if (3 * (int64_t)batch * (n > m ? n : m) >= kMaxElems) return fail(S3R_ERR_INVALID, "tensor of 2^31 elements or more: split the batch");
+    hipStream_t s = (hipStream_t)stream;
+    // per computed direction: 7 per target (one doubling, 3 differences, 3 products: the own term) + 10 per source (one doubling, 3
+    // differences, 3 products, 3 adds: every source scatters one term); the index compares of the scan are not counted
+    const double B = batch, N = n, M = m;
+    const double flops = B * ((grad_p ? 7.0 * N + 10.0 * M : 0.0) + (grad_q ? 7.0 * M + 10.0 * N : 0.0));
+    const double elems = 3.0 * (N + M) + (N + M) + (grad_dist1 ? N : 0.0) + (grad_dist2 ? M : 0.0) + (grad_p ? 3.0 * N : 0.0) +
+                         (grad_q ? 3.0 * M : 0.0);
+    ProfScope ps(s, F_CHAMFER, 1, flops, 4.0 * B * elems);
+    hipError_t e = s3r::launch_chamfer_backward(p, q, idx1, idx2, grad_dist1, grad_dist2, grad_p, grad_q, batch, n, m, s);
+    if (e != hipSuccess) return hip_fail(e, "chamfer backward launch");
+    return S3R_OK;
+}
+
 int s3r_voxel_iou(const float* pred, const float* gt, float threshold, float* iou, int batch, int64_t voxels,
                   void* stream) {
     if (!pred || !gt || !iou) return fail(S3R_ERR_INVALID, "null tensor pointer");

@@ -263,6 +263,9 @@ hipError_t launch_head(const float* x, const float* w, const float* scale, const
                        int64_t S, int act, hipStream_t s);
 hipError_t launch_chamfer(const float* p, const float* q, float* d1, float* d2, int* i1, int* i2,
                           int B, int N, int M, hipStream_t s);
+// the gather-form backward (fixed summation order, no atomics); g1 or g2 NULL: zeros; gp or gq NULL: that direction is not computed
+hipError_t launch_chamfer_backward(const float* p, const float* q, const int* i1, const int* i2, const float* g1, const float* g2,
+                                   float* gp, float* gq, int B, int N, int M, hipStream_t s);
 // scratch: linear_scratch_elems floats of split-K slabs
 hipError_t launch_linear(const float* x, const float* w, const float* scale, const float* bias, float* y, int B,
                          int Cin, int Cout, int act, float* scratch, hipStream_t s);

@@ -857,13 +857,81 @@ def chamfer_distance(p: torch.Tensor, q: torch.Tensor):
     return d1, d2, i1, i2
 
 
+@torch.no_grad()
+def chamfer_distance_backward(p: torch.Tensor, q: torch.Tensor, idx1: torch.Tensor, idx2: torch.Tensor, grad_dist1, grad_dist2,
+                              need_p: bool = True, need_q: bool = True):
+    """(grad_p (B,N,3) or None, grad_q (B,M,3) or None) of sum(grad_dist1 * dist1) + sum(grad_dist2 * dist2), the indices of
+    `chamfer_distance` held fixed (`s3r_chamfer_backward`): a gather with a fixed summation order — own term first, then the
+    scattered terms in ascending source index, fp32, no fused multiply-adds, no atomics — so the bits do not depend on the run or on
+    the batch split.  grad_dist1 / grad_dist2: (B,N) / (B,M) fp32, or None for zeros (not both); need_p / need_q: the sides to compute."""
+    if p.dim() != 3 or q.dim() != 3 or p.shape[-1] != 3 or q.shape[-1] != 3 or p.shape[0] != q.shape[0]:
+        raise RuntimeError(f"chamfer_distance_backward expects (B,N,3) and (B,M,3), got {tuple(p.shape)} and {tuple(q.shape)}")
+    p = _check_input(p, "p", p.shape[1:])
+    q = _check_input(q, "q", q.shape[1:])
+    B, N, M = p.shape[0], p.shape[1], q.shape[1]
+    if N == 0 or M == 0:
+        raise RuntimeError("chamfer_distance_backward needs non-empty point clouds")
+    if grad_dist1 is None and grad_dist2 is None:
+        raise RuntimeError("chamfer_distance_backward needs grad_dist1 or grad_dist2")
+    if not (need_p or need_q):
+        raise RuntimeError("chamfer_distance_backward needs need_p or need_q")
+    idx1 = _check_input(idx1, "idx1", (N,), torch.int32)
+    idx2 = _check_input(idx2, "idx2", (M,), torch.int32)
+    g1 = None if grad_dist1 is None else _check_input(grad_dist1, "grad_dist1", (N,))
+    g2 = None if grad_dist2 is None else _check_input(grad_dist2, "grad_dist2", (M,))
+    for t, name in ((idx1, "idx1"), (idx2, "idx2"), (g1, "grad_dist1"), (g2, "grad_dist2")):
+        if t is not None and t.shape[0] != B:
+            raise RuntimeError(f"{name} must have batch {B}, got {tuple(t.shape)}")
+    gp = torch.empty((B, N, 3), dtype=torch.float32, device=p.device) if need_p else None
+    gq = torch.empty((B, M, 3), dtype=torch.float32, device=p.device) if need_q else None
+    if B:
+        ptr = [None if t is None else t.data_ptr() for t in (g1, g2, gp, gq)]
+        _lib.check(_lib.load().s3r_chamfer_backward(p.data_ptr(), q.data_ptr(), idx1.data_ptr(), idx2.data_ptr(), *ptr, B, N, M,
+                                                    _stream_ptr(p.device)), "chamfer backward")
+    return gp, gq
+
+
+class _ChamferFunction(torch.autograd.Function):
+    """`chamfer_distance` with `chamfer_distance_backward` as its derivative (the indices are constants of the graph)"""
+
+    @staticmethod
+    def forward(ctx, p, q):
+        d1, d2, i1, i2 = chamfer_distance(p, q)
+        ctx.mark_non_differentiable(i1, i2)
+        ctx.set_materialize_grads(False)                           # an unused dist1 / dist2 arrives as None: NULL, not a zero tensor
+        ctx.save_for_backward(p, q, i1, i2)
+        return d1, d2, i1, i2
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g1, g2, _gi1, _gi2):
+        p, q, i1, i2 = ctx.saved_tensors
+        need_p, need_q = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (g1 is None and g2 is None) or not (need_p or need_q):
+            return None, None
+        g1 = None if g1 is None else g1.contiguous().float()
+        g2 = None if g2 is None else g2.contiguous().float()
+        return chamfer_distance_backward(p, q, i1, i2, g1, g2, need_p, need_q)
+
+
+def differentiable_chamfer_distance(p: torch.Tensor, q: torch.Tensor):
+    """`chamfer_distance` recorded for autograd: (dist1, dist2, idx1, idx2), the same bits; dist1 / dist2 carry the deterministic
+    backward `chamfer_distance_backward`, idx1 / idx2 are non-differentiable."""
+    return _ChamferFunction.apply(p, q)
+
+
 class ChamferDistance(nn.Module):
     """Drop-in for the reference's extensions/chamfer_dist module (README.md:64-65): forward(p, q)
     returns mean(dist1) + mean(dist2).  (Whether the reference reduces with mean or sum, squared or
-    not, is unknown — SURVEY.md §8a row 5; `chamfer_distance` exposes the unreduced tensors.)"""
+    not, is unknown — SURVEY.md §8a row 5; `chamfer_distance` exposes the unreduced tensors.)
+    A loss as well as a metric: with grad mode on and p or q requiring grad the value (the same bits) is recorded for autograd
+    through `differentiable_chamfer_distance`; otherwise nothing is recorded."""
 
     def forward(self, p, q):
-        d1, d2, _, _ = chamfer_distance(p, q)
+        if torch.is_grad_enabled() and (p.requires_grad or q.requires_grad):
+            d1, d2, _, _ = differentiable_chamfer_distance(p, q)
+        else:
+            d1, d2, _, _ = chamfer_distance(p, q)
         return d1.mean() + d2.mean()
 
 
