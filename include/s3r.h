@@ -287,7 +287,19 @@ int64_t s3r_linear_scratch_elems(int batch, int cin, int cout);
 int s3r_linear_forward(const float* x, const float* w, const float* bias, float* y, int batch, int cin, int cout,
                        int act, float* scratch, int64_t scratch_elems, void* stream);
 
-/* squared-L2 nearest neighbours both ways; p (B,N,3), q (B,M,3) */
+/* squared-L2 nearest neighbours both ways; p (B,N,3), q (B,M,3); dist1, idx1 (B,N): for every point of p its nearest point of q;
+ * dist2, idx2 (B,M): the reverse.  The rule, which s3r_chamfer_backward's "same bits for every batch split" rests on:
+ *   - the distance of a pair is ((dx*dx + dy*dy) + dz*dz) in fp32, dx = p.x - q.x and so on: eight operations, each rounded once, in
+ *     this order, nothing fused;
+ *   - dist is the smallest distance of the query and idx its FIRST minimum: the lowest index of the other cloud that holds that
+ *     smallest distance (equal distances are common: duplicated points, points on a grid), whatever the cloud sizes — the result
+ *     is that of one sequential scan in ascending index that replaces its best only on a strictly smaller distance;
+ *   - minima are taken over the distances that are not NaN (IEEE minNum): a NaN distance (a NaN coordinate, inf - inf) is skipped;
+ *   - a query with no candidate below +inf — its own coordinates are not finite, or every candidate's are not — gets
+ *     dist = +inf, idx = 0;
+ *   - inputs are expected finite.  A non-finite point is not an error here, and it cannot hide: its own distance is +inf, so
+ *     it shows up as a non-finite loss (s3r.ChamferDistance: mean(dist1) + mean(dist2)), while the other points' answers are
+ *     those of the cloud without it.  (torch.min, which the oracle uses, propagates NaN instead: the two differ on NaN only.) */
 int s3r_chamfer_forward(const float* p, const float* q, float* dist1, float* dist2, int32_t* idx1, int32_t* idx2,
                         int batch, int n, int m, void* stream);
 
@@ -312,7 +324,12 @@ int s3r_chamfer_forward(const float* p, const float* q, float* dist1, float* dis
 int s3r_chamfer_backward(const float* p, const float* q, const int32_t* idx1, const int32_t* idx2, const float* grad_dist1,
                          const float* grad_dist2, float* grad_p, float* grad_q, int batch, int n, int m, void* stream);
 
-/* per-sample IoU of (pred > th) vs (gt > th) over `voxels` elements */
+/* per-sample IoU of (pred > th) vs (gt > th) over `voxels` elements.  A voxel is occupied iff its value is strictly greater than
+ * `threshold`, compared in fp32 — the threshold is the caller's value rounded to fp32 (0.2, 0.3 and 0.4 are not fp32 numbers: a voxel
+ * holding float32(0.3) is NOT occupied at 0.3, although it is greater than the real number 0.3).  NaN is not occupied; -0.0 equals
+ * +0.0; +inf is occupied at every finite threshold.  The two counts are exact integers (< 2^32); the result is
+ * float32(intersection) / float32(union), both conversions round-to-nearest-even (they round from 2^24 voxels up), one fp32 division;
+ * 1 when the union is empty. */
 int s3r_voxel_iou(const float* pred, const float* gt, float threshold, float* iou, int batch, int64_t voxels,
                   void* stream);
 

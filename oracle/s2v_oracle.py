@@ -177,6 +177,8 @@ def chamfer_distance(p: torch.Tensor, q: torch.Tensor):
     p (B,N,3), q (B,M,3) -> dist1 (B,N) = min_j |p_i-q_j|^2, dist2 (B,M) = min_i |p_i-q_j|^2,
     idx1 (B,N) int32, idx2 (B,M) int32 (first minimum).  Computed in the difference form
     (dx^2+dy^2+dz^2), not the |p|^2+|q|^2-2pq expansion, so fp32 results are well conditioned.
+    torch.min propagates NaN (a query with one NaN distance answers NaN, at that index); s3r_chamfer_forward takes the minimum over
+    the distances that are not NaN.  The two agree bit for bit wherever no distance is NaN (tests/_select_ref.py states the rule).
     """
     d = (p[:, :, None, :] - q[:, None, :, :])
     d = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]

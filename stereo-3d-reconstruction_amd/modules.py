@@ -838,7 +838,11 @@ class Stereo2Point(_DisparityMixin, nn.Module):
 
 @torch.no_grad()
 def chamfer_distance(p: torch.Tensor, q: torch.Tensor):
-    """(dist1 (B,N), dist2 (B,M), idx1 (B,N) int32, idx2 (B,M) int32): squared-L2 nearest neighbours."""
+    """(dist1 (B,N), dist2 (B,M), idx1 (B,N) int32, idx2 (B,M) int32): squared-L2 nearest neighbours (`s3r_chamfer_forward`).
+    The distance is ((dx*dx + dy*dy) + dz*dz) in fp32, each operation rounded once.  idx is the FIRST minimum: the lowest index
+    holding the smallest distance, as one sequential scan with a strict `<` finds it.  Minima are taken over the distances that are
+    not NaN (IEEE minNum); a query with no candidate below +inf gets dist = +inf, idx = 0.  Inputs are expected finite: a
+    non-finite point has the distance +inf itself, so it shows up as a non-finite loss and never hides behind a finite one."""
     if p.dim() != 3 or q.dim() != 3 or p.shape[-1] != 3 or q.shape[-1] != 3 or p.shape[0] != q.shape[0]:
         raise RuntimeError(f"chamfer_distance expects (B,N,3) and (B,M,3), got {tuple(p.shape)} and {tuple(q.shape)}")
     p = _check_input(p, "p", p.shape[1:])
@@ -937,7 +941,10 @@ class ChamferDistance(nn.Module):
 
 @torch.no_grad()
 def voxel_iou(pred: torch.Tensor, gt: torch.Tensor, threshold: float = 0.5) -> torch.Tensor:
-    """Per-sample IoU of (pred > th) vs (gt > th), computed on the device: (B,...) -> (B,)."""
+    """Per-sample IoU of (pred > th) vs (gt > th), computed on the device: (B,...) -> (B,) (`s3r_voxel_iou`).  Occupied means
+    strictly greater than the threshold ROUNDED TO fp32, compared in fp32 (a voxel holding float32(0.3) is not occupied at 0.3);
+    NaN is not occupied.  The counts are exact; the result is float32(intersection) / float32(union), conversions
+    round-to-nearest-even, 1 for an empty union."""
     if pred.shape != gt.shape:
         raise RuntimeError("pred and gt shapes differ")
     pred = _check_input(pred, "pred", pred.shape[1:])
