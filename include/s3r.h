@@ -108,8 +108,24 @@ typedef enum s3r_act { S3R_ACT_NONE = 0, S3R_ACT_RELU = 1, S3R_ACT_SIGMOID = 2,
  *                      column class a, row class b of the 6 x 6 window of padded rows 4 q .. 4 q + 5 and padded columns
  *                      4 s .. 4 s + 5 (rows first, then columns).  It is also the one OUTPUT layout other than PLAIN: a
  *                      two-axis Conv2d whose consumer is another one writes these plane sets of its own (halo-1) output from
- *                      its finish kernel — s3r_chain_forward plans that hand-off itself (e6 -> e7 of this network). */
-typedef enum s3r_layout { S3R_LAYOUT_PLAIN = 0, S3R_LAYOUT_WINO_H = 2, S3R_LAYOUT_WINO_DH = 3, S3R_LAYOUT_WINO_HW = 4 } s3r_layout;
+ *                      its finish kernel — s3r_chain_forward plans that hand-off itself (e6 -> e7 of this network).
+ *   S3R_LAYOUT_WINO_3D the operand of ANY 3D two-axis layer exactly as that layer's own input transform lays it out, partial last
+ *                      groups included: (ncls, B, C, G, G, n + 2 h) with h = in_halo = pad — Conv3d k3 s1 p1: ncls 36, G =
+ *                      ceil(n / 4), windows of padded depths / rows 4 s .. 4 s + 5; Conv3d k4 s1 p0: ncls 25, G = ceil((n - 3) / 2),
+ *                      windows 2 s .. 2 s + 4; rows and depths beyond the padded tensor read as 0.  As an OUTPUT layout it is the
+ *                      same tensor written by the producer in place of its plain activation, which then does not exist; out_halo
+ *                      (1 / 0) says which of the two consumers it is for.
+ *   S3R_LAYOUT_DIFF    the operand of the Winograd form of a ConvTranspose3d k4 s2 p1 (in_halo 1): (4, B, C, n+2, n+2, n+2) — the
+ *                      halo-padded plain tensor x, then Dh[z][r] = x[z][r] - x[z][r+1], Dd[z][r] = x[z][r] - x[z+1][r] and
+ *                      Ddh[z][r] = Dh[z][r] - Dh[z+1][r] over the whole padded volume (0 in the last row / depth).  As an OUTPUT
+ *                      layout: the four tensors written by the producer (out_halo 1).
+ *                      Both are written by ONE pass that replaces the producer's finish pass and the consumer's operand pass — a
+ *                      split-K direct convolution, a class-parallel two-axis Conv3d or a class-parallel transposed Winograd layer
+ *                      in front of such a consumer — with the bits the two passes give.  s3r_chain_forward plans these hand-offs
+ *                      itself (v4 -> v5 -> v6 -> d1 -> d2 of this network) where both layers' algorithms and launch forms allow it;
+ *                      a single-layer call that asks for one its launch form cannot serve fails with S3R_ERR_INVALID. */
+typedef enum s3r_layout { S3R_LAYOUT_PLAIN = 0, S3R_LAYOUT_WINO_H = 2, S3R_LAYOUT_WINO_DH = 3, S3R_LAYOUT_WINO_HW = 4,
+                          S3R_LAYOUT_WINO_3D = 5, S3R_LAYOUT_DIFF = 6 } s3r_layout;
 
 /* Which convolution algorithm a layer's forward runs (ABI 7).  The fp32 3 x 3 [x 3] stride-1 pad-1 convolutions and the
  * transposed convolutions have two kernels — the direct implicit GEMM and a Winograd form with 1/2 .. 9/16 of the
@@ -146,7 +162,8 @@ typedef enum s3r_algo { S3R_ALGO_AUTO = 0, S3R_ALGO_DIRECT = 1, S3R_ALGO_WINOGRA
  * interiors only, so a buffer zeroed once keeps its halo.  Two writers store whole padded rows instead (whole 128-byte lines:
  * partial lines cost a read-modify-write) and so rewrite the halo rows / columns of the planes they write with +0.0, the value
  * the halo holds: the two-axis Winograd Conv2d (its finish kernel) and the fp32 s3r_cost_volume_forward.  Neither ever writes
- * anything but +0.0 there, nor a halo PLANE (depth) of a 3D output.  s3r_chain_forward plans the halos of all
+ * anything but +0.0 there, nor a halo PLANE (depth) of a 3D output.  (The plain tensor inside an S3R_LAYOUT_DIFF output is written
+ * whole, every halo element with +0.0: that layout exists between two layers of a chain only.)  s3r_chain_forward plans the halos of all
  * intermediates itself and pads an unpadded chain input on the fly. */
 typedef struct s3r_conv_desc {
     int32_t op;        /* s3r_op */
@@ -166,8 +183,10 @@ typedef struct s3r_conv_desc {
     int32_t ksplit;    /* 0: library picks; >=1: force the split-K factor (must divide cin/16; bf16: cin/32) */
     int32_t dtype;     /* s3r_dtype: which path (layout + matrix instruction) the layer runs on */
     int32_t in_layout; /* s3r_layout of the input buffer: PLAIN, or the plane sets a producer wrote for this layer's Winograd kernel —
-                          WINO_H (one-axis), WINO_DH (two-axis Conv3d), WINO_HW (two-axis Conv2d); in_halo must be 1 for those */
-    int32_t out_layout;/* s3r_layout of the output buffer: PLAIN, or WINO_HW (a two-axis Conv2d writing its consumer's plane sets) */
+                          WINO_H (one-axis), WINO_DH (two-axis Conv3d), WINO_HW (two-axis Conv2d): in_halo must be 1 for those;
+                          WINO_3D (any two-axis Conv3d, in_halo = pad), DIFF (transposed Winograd form, in_halo 1) */
+    int32_t out_layout;/* s3r_layout of the output buffer: PLAIN, WINO_HW (a two-axis Conv2d writing its consumer's plane sets), or
+                          WINO_3D / DIFF (a 3D layer writing its consumer's operand from its finish pass) */
     int32_t algo;      /* s3r_algo (ABI 7): AUTO = the library's geometry-only policy */
     /* ABI 8 — parameter-general layers (fp32 path).  The shapes this build's network has keep their tuned kernels; any other
      * (k, stride, pad, dilation) convolution with cin % 16 == 0 runs the direct kernel; everything else listed here goes through

@@ -24,9 +24,15 @@ int wino2_run(const s3r_conv_desc* d, const Geo& g, s3r::ConvParams p, const flo
               int64_t scratch_elems, int form, hipStream_t s, int* launches) {
     const Wino2Geo g2 = wino2_geo(d);
     const WinoNeed need = wino2_need(d, form);
-    const bool pre = d->in_layout == S3R_LAYOUT_WINO_DH || d->in_layout == S3R_LAYOUT_WINO_HW;      // the producer wrote the plane sets
+    const bool pre = d->in_layout == S3R_LAYOUT_WINO_DH || d->in_layout == S3R_LAYOUT_WINO_HW ||
+                     d->in_layout == S3R_LAYOUT_WINO_3D;             // the producer wrote the plane sets
     const bool to_v = d->out_layout == S3R_LAYOUT_WINO_HW;           // ... and this layer writes its consumer's
-    if (g2.bmax <= 0 || ((pre || to_v) && g2.bmax < d->batch))
+    // ... or (3D) its consumer's operand from ONE pass in place of the finish pass: ConvParams::out_mode
+    p.out_mode = d->out_layout == S3R_LAYOUT_WINO_3D ? (d->out_halo ? 1 : 2) : d->out_layout == S3R_LAYOUT_DIFF ? 3 : 0;
+    if (p.out_mode && (g2.ax > 1 || wino2_form_of(d, (int)(g2.pos_sample * d->batch), form) != 0))
+        return fail(S3R_ERR_INVALID, "a consumer's operand is written from the class-parallel launch form of a 3D two-axis layer only (the semi-fused "
+                    "form of this batch keeps the plain output: s3r_chain_forward plans that itself)");
+    if (g2.bmax <= 0 || ((pre || to_v || p.out_mode) && g2.bmax < d->batch))
         return fail(S3R_ERR_INVALID, "two-axis Winograd form: the transformed input of this batch exceeds 2 GiB (at most %d samples per "
                     "call with a producer-written input: s3r_conv_wino_input_elems)", g2.bmax);
     if (!scratch || scratch_elems < need.total)
@@ -89,16 +95,19 @@ int dwino_run(const s3r_conv_desc* d, s3r::ConvParams p, const float* x, const f
         return fail(S3R_ERR_WORKSPACE, "the Winograd form of this transposed convolution needs %lld floats of scratch "
                     "(s3r_conv_scratch_elems), got %lld", (long long)need.total, (long long)(scratch ? scratch_elems : 0));
     const int n = d->in_size;
-    p.xd_mode = dwino_materialise(d) ? 1 : 0;
-    hipError_t e;
-    {
-        const double x_el = (double)d->batch * d->cin * (double)ipow(n + 2, 3);
-        s3r::AuxScope aux(s, 4.0 * x_el * (p.xd_mode ? 4.0 : 2.0));      // (reads x, writes Dh [, Dd, Ddh])
+    const bool pre = d->in_layout == S3R_LAYOUT_DIFF;                 // the producer wrote [x | Dh | Dd | Ddh]
+    const int64_t x_plain = (int64_t)d->batch * d->cin * ipow(n + 2, 3);
+    p.xd_mode = pre || dwino_materialise(d) ? 1 : 0;
+    hipError_t e = hipSuccess;
+    if (!pre) {
+        s3r::AuxScope aux(s, 4.0 * (double)x_plain * (p.xd_mode ? 4.0 : 2.0));      // (reads x, writes Dh [, Dd, Ddh])
         e = s3r::launch_wino_diff(x, scratch, (long long)d->batch * d->cin, n + 2, n + 2, n + 2, p.xd_mode, s);
     }
     if (e != hipSuccess) return hip_fail(e, "Winograd difference-tensor launch");
     p.x = x;
-    p.xd = scratch;
+    p.xd = pre ? x + x_plain : scratch;
+    p.x_bytes = (unsigned)(4 * x_plain);                              // (one tensor: the class kernel steps from Dh to Dd to Ddh by it)
+    p.out_mode = d->out_layout == S3R_LAYOUT_DIFF ? 3 : 0;            // ... and this layer's finish pass writes its consumer's
     p.part = scratch + need.v;
     p.w = packed_w + 64 * (int64_t)d->cin * cout_pad(d->cout);          // behind the direct slab (8 classes x 8 taps)
     p.Nd = n / 2; p.Nh = n / 2;
@@ -109,10 +118,13 @@ int dwino_run(const s3r_conv_desc* d, s3r::ConvParams p, const float* x, const f
     p.dW = s3r::FastDiv((unsigned)p.Nw);
     p.ksplit = 1;
     const s3r::WinoLaunch L = s3r::wino_plan(2, d->cout, wino_kcls(d), p.Ntotal, p.head_w != nullptr, form);
+    if (p.out_mode && (L.mode != s3r::WINO_CP || p.head_w))
+        return fail(S3R_ERR_INVALID, "a consumer's difference tensors are written from the class-parallel launch form of the transposed Winograd "
+                    "layer only (the form of this batch keeps the plain output: s3r_chain_forward plans that itself)");
     int nl = 0;
     e = s3r::launch_deconv_wino(p, L, s, &nl);
     if (e != hipSuccess) return hip_fail(e, "Winograd transposed-conv launch");
-    *launches = 1 + nl;
+    *launches = (pre ? 0 : 1) + nl;
     *ran = 1 + L.mode;
     return S3R_OK;
 }
@@ -580,6 +592,14 @@ int conv_forward_impl(const s3r_conv_desc* d, const void* xv, const void* x2v, i
             }
             Launch L;
             if ((rc = resolve_launch(d, &p, &L))) return rc;
+            if (d->in_layout != S3R_LAYOUT_PLAIN || d->out_layout == S3R_LAYOUT_DIFF || d->out_layout == S3R_LAYOUT_WINO_HW)
+                return fail(S3R_ERR_INVALID, "the direct kernel reads a plain input and writes a plain output or (split-K) its consumer's two-axis plane sets");
+            if (d->out_layout == S3R_LAYOUT_WINO_3D) {      // the split-K finish pass writes the consumer's plane sets
+                if (L.ksplit <= 1 || d->op != S3R_OP_CONV || needs_act_pass(d) || p.act == S3R_ACT_SIGMOID)
+                    return fail(S3R_ERR_INVALID, "a direct layer writes its consumer's plane sets from its split-K finish pass only (convolution, "
+                                "ksplit > 1, no activation pass behind it)");
+                p.out_mode = d->out_halo ? 1 : 2;
+            }
             if (L.ksplit > 1) {
                 const int64_t need = s3r::conv_scratch_elems(p, L.cfg);
                 if (scratch && scratch_elems >= need) p.part = scratch;

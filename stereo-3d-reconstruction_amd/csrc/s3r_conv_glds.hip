@@ -787,7 +787,12 @@ static hipError_t launch_cfg(ConvParams p, hipStream_t stream) {
         dim3 grid(p.m_tiles * p.n_tiles * (p.transposed ? 8 : 1), 1, p.ksplit);      // (class inside blockIdx.x)
         hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, VEC, HEAD, NBUF>), grid, dim3(256), lds, stream, p);
         hipError_t e = hipGetLastError();
-        if (e == hipSuccess && p.ksplit > 1) e = launch_conv_finish(p, p.n_tiles * BN, stream);
+        if (e == hipSuccess && p.ksplit > 1) {
+            if (p.out_mode) {      // the finish pass writes the consumer's plane sets (s3r_conv_wino.hip): in place of conv_finish_kernel
+                g_launch_count += 1;
+                e = launch_wino_handoff(p, 3, p.out_mode - 1, p.n_tiles * BN, stream);
+            } else e = launch_conv_finish(p, p.n_tiles * BN, stream);
+        }
         return e;
     }
 }
@@ -931,6 +936,7 @@ hipError_t launch_conv_mfma(const ConvParams& pin, int code, hipStream_t stream)
     if (vec > vmax) vec = vmax;
     if (p.Cin % GBK != 0 || p.Ntotal % vec != 0) return hipErrorInvalidValue;
     if (p.ksplit < 1 || (p.Cin / GBK) % p.ksplit != 0 || (p.ksplit > 1 && !p.part)) return hipErrorInvalidValue;
+    if (p.out_mode && (p.ksplit <= 1 || p.head_w || p.transposed)) return hipErrorInvalidValue;      // (only the split-K finish hands off)
     if (p.head_w) {   // fused head: one wave must hold all couts of its positions (WM == 1, BM >= Cout), no split-K
         int bm, bn;
         conv_tile_dims(cfg, &bm, &bn);

@@ -70,6 +70,8 @@ struct Plan {
     std::vector<Geo> g;
     std::vector<int64_t> off;         // workspace offset of layer i's OUTPUT (-1: the caller's y)
     std::vector<char> fuse_head;      // layer i is an MFMA conv whose epilogue also runs layer i+1 (1x1 head)
+    std::vector<int64_t> region;      // storage of layer i's output region where it is more than g[i].y_store (a 3D hand-off pair: the
+                                      // larger of the plain output and the consumer's operand, whichever the launch forms pick), else 0
     bool stem_wino = false;           // the stem writes layer 1's Winograd-transformed planes (launch_stem_wino), not its activation
     bool pad_input = false;
     int64_t pad_off = 0;

@@ -132,6 +132,11 @@ struct ConvParams {
     // depth differences Dd and the mixed differences Ddh (materialised), 0: those are formed inside the class kernel
     const float* xd;
     int xd_mode;
+    // hand-off (s3r_conv_wino.hip, launch_wino_handoff): 0 the layer's own finish pass writes the plain output; 1 + cons: ONE pass
+    // finishes the raw sums in `part` and writes the CONSUMER's operand to y — cons 0 / 1 the two-axis plane sets of a Conv3d k3 p1 /
+    // k4 p0, 2 [x | Dh | Dd | Ddh] of a transposed Winograd layer; y_hs / y_ds / y_cs / y_org still describe the halo-padded plain
+    // output, which is the consumer's input geometry
+    int out_mode;
 };
 
 // The residue classes of a general ConvTranspose (s3r_general.hip) as ONE launch of the direct kernel: workgroup ranges of a class
@@ -212,6 +217,11 @@ int wino2_form(int ax, int cout, int ntotal, int forced);                      /
 int64_t wino2_slab_elems(int ax, int cout, int ntotal, int form);
 int64_t wino2_npad(int64_t ntotal);                                           // positions rounded up to whole GEMM tiles
 hipError_t launch_conv_wino2(ConvParams p, int ax, int form, bool to_v, hipStream_t stream, int* launches);   // to_v: write the next layer's plane sets
+// One pass in place of a producer's finish pass and its consumer's operand pass (3D, same bits as the two): a workgroup finishes a
+// block of couts of one sample into LDS as the consumer's halo-padded input, then writes the consumer's operand from there.
+// prod: 0 / 1 the class slabs of a class-parallel two-axis Conv3d (ax 0 / 1), 2 those of a class-parallel transposed Winograd layer,
+// 3 the split-K partial slabs of a direct convolution; cons: see ConvParams::out_mode; npad: positions per slab row
+hipError_t launch_wino_handoff(const ConvParams& p, int prod, int cons, int npad, hipStream_t stream);
 // the cost volume written as the 36 two-axis plane sets of its halo-1 padded form: V[36][B][2C][(D)/4][H/4][W+2]
 hipError_t launch_cost_volume_wino2(const float* fl, const float* fr, float* V, int B, int C, int D, int H, int W, hipStream_t s);
 int wino_bk();                      // channels per K tile of the Winograd kernels (Cin must be a multiple)

@@ -153,7 +153,9 @@ int geometry(const s3r_conv_desc* d, Geo* g) {
         return fail(S3R_ERR_INVALID, "halo must be in [0, 8]");
     if (d->dtype != S3R_F32 && d->dtype != S3R_BF16) return fail(S3R_ERR_INVALID, "unknown dtype %d", d->dtype);
     if ((d->in_layout != S3R_LAYOUT_PLAIN && d->in_layout != S3R_LAYOUT_WINO_H && d->in_layout != S3R_LAYOUT_WINO_DH &&
-         d->in_layout != S3R_LAYOUT_WINO_HW) || (d->out_layout != S3R_LAYOUT_PLAIN && d->out_layout != S3R_LAYOUT_WINO_HW))
+         d->in_layout != S3R_LAYOUT_WINO_HW && d->in_layout != S3R_LAYOUT_WINO_3D && d->in_layout != S3R_LAYOUT_DIFF) ||
+        (d->out_layout != S3R_LAYOUT_PLAIN && d->out_layout != S3R_LAYOUT_WINO_HW && d->out_layout != S3R_LAYOUT_WINO_3D &&
+         d->out_layout != S3R_LAYOUT_DIFF))
         return fail(S3R_ERR_INVALID, "unknown layout");
     if ((d->in_layout || d->out_layout) && d->op == S3R_OP_LINEAR)
         return fail(S3R_ERR_INVALID, "the transformed input layout exists on the convolution paths only");
@@ -230,6 +232,32 @@ int geometry(const s3r_conv_desc* d, Geo* g) {
         if (d->dtype != S3R_F32 || d->op != S3R_OP_CONV || d->ndim != 2 || (g->out & 3) || d->cout % 32 != 0 || d->act == S3R_ACT_SIGMOID)
             return fail(S3R_ERR_INVALID, "the two-axis Winograd output layout is written by an fp32 Conv2d with an output edge %% 4 == 0 and cout %% 32 == 0");
         g->y_elems = 36 * (int64_t)d->cout * s3r::wino2_npad((int64_t)d->batch * (g->out / 4) * (g->out / 4));
+    }
+    if (d->in_layout == S3R_LAYOUT_WINO_3D) {    // the plane sets of any 3D two-axis layer, partial last groups included
+        const int ax = wino2_ax(d);
+        if ((ax != 0 && ax != 1) || d->in_halo != d->pad)
+            return fail(S3R_ERR_INVALID, "the general two-axis Winograd input layout serves an fp32 Conv3d k=3 s=1 p=1 / k=4 s=1 p=0 with cin %% %d == 0, "
+                        "in_halo = pad", s3r::wino_bk());
+        g->x_elems = wino2_geo(d).v_sample * d->batch;
+    }
+    if (d->in_layout == S3R_LAYOUT_DIFF) {       // [x | Dh | Dd | Ddh] of the transposed Winograd form
+        if (!dwino_layer(d) || d->in_halo != 1)
+            return fail(S3R_ERR_INVALID, "the difference-tensor input layout serves the Winograd form of an fp32 ConvTranspose3d k=4 s=2 p=1 over an "
+                        "edge %% 4 == 0, in_halo = 1");
+        g->x_elems *= 4;
+    }
+    if (d->out_layout == S3R_LAYOUT_WINO_3D || d->out_layout == S3R_LAYOUT_DIFF) {      // ... written by the layer in front of such a consumer
+        const bool diff = d->out_layout == S3R_LAYOUT_DIFF;
+        if (d->dtype != S3R_F32 || d->ndim != 3 || d->cout % s3r::wino_bk() != 0 || d->act > S3R_ACT_RELU ||
+            (diff ? d->out_halo != 1 || (g->out & 3) : d->out_halo > 1 || g->out < (d->out_halo ? 4 : 5)))
+            return fail(S3R_ERR_INVALID, "a consumer's operand is written by an fp32 3D layer with cout %% %d == 0, no activation or ReLU, and the halo the "
+                        "consumer reads (two-axis planes: out_halo 1 for k3 p1, 0 for k4 p0; difference tensors: out_halo 1, output edge %% 4 == 0)",
+                        s3r::wino_bk());
+        if (diff) g->y_elems *= 4;
+        else {
+            const int sg = d->out_halo ? (g->out + 3) / 4 : (g->out - 2) / 2;
+            g->y_elems = (int64_t)(d->out_halo ? 36 : 25) * d->batch * d->cout * sg * sg * g->out_p;
+        }
     }
     g->w_elems = (int64_t)d->cin * d->cout * ipow(d->k, g->nd);
     if (d->op == S3R_OP_DECONV)
@@ -333,8 +361,10 @@ int64_t dwino3_w_offset(const s3r_conv_desc* d) {
 // the descriptor can run its layer's Winograd form
 bool wino_desc_ok(const s3r_conv_desc* d) {
     if (!(wino_layer(d) || dwino_layer(d)) || d->act >= S3R_ACT_SIGMOID || d->in_halo != 1 || d->ksplit > 1 || dil_of(d) != 1) return false;
-    if (d->out_layout != S3R_LAYOUT_PLAIN) return false;
-    return d->in_layout == S3R_LAYOUT_PLAIN || (d->in_layout == S3R_LAYOUT_WINO_H && wino_layer(d));
+    // (a transposed layer may read its operand from, and write its consumer's to, the difference-tensor layout)
+    if (d->out_layout != S3R_LAYOUT_PLAIN && !(d->out_layout == S3R_LAYOUT_DIFF && dwino_layer(d))) return false;
+    return d->in_layout == S3R_LAYOUT_PLAIN || (d->in_layout == S3R_LAYOUT_WINO_H && wino_layer(d)) ||
+           (d->in_layout == S3R_LAYOUT_DIFF && dwino_layer(d));
 }
 // Two-axis class-parallel Winograd (s3r_conv_wino.hip): the stride-1 layers with a small edge — Conv3d k3 p1 as F(4,3) x F(4,3)
 // over D and H (returns 0), Conv3d k4 p0 as F(2,4) x F(2,4) (returns 1), Conv2d k3 p1 as F(4,3) x F(4,3) over H and W (returns 2);
@@ -351,8 +381,22 @@ int wino2_ax(const s3r_conv_desc* d) {
 bool wino2_desc_ok(const s3r_conv_desc* d) {
     return wino2_ax(d) >= 0 && d->act < S3R_ACT_SIGMOID && dil_of(d) == 1 && d->in_halo == d->pad && d->ksplit <= 1 &&
            (d->in_layout == S3R_LAYOUT_PLAIN || (d->in_layout == S3R_LAYOUT_WINO_DH && wino2_ax(d) == 0 && d->in_size % 4 == 0) ||
-            (d->in_layout == S3R_LAYOUT_WINO_HW && wino2_ax(d) == 2 && d->in_size % 4 == 0)) &&
-           (d->out_layout == S3R_LAYOUT_PLAIN || (d->out_layout == S3R_LAYOUT_WINO_HW && wino2_ax(d) == 2 && d->in_size % 4 == 0));
+            (d->in_layout == S3R_LAYOUT_WINO_HW && wino2_ax(d) == 2 && d->in_size % 4 == 0) ||
+            (d->in_layout == S3R_LAYOUT_WINO_3D && wino2_ax(d) <= 1)) &&
+           (d->out_layout == S3R_LAYOUT_PLAIN || (d->out_layout == S3R_LAYOUT_WINO_HW && wino2_ax(d) == 2 && d->in_size % 4 == 0) ||
+            ((d->out_layout == S3R_LAYOUT_WINO_3D || d->out_layout == S3R_LAYOUT_DIFF) && wino2_ax(d) <= 1));
+}
+// the descriptor asks for the direct kernel
+static bool forced_direct(const s3r_conv_desc* d) {
+    return d->algo == S3R_ALGO_DIRECT || (d->algo == S3R_ALGO_AUTO && (d->tile >= 0 || d->ksplit >= 1));
+}
+// a layout only the two-axis kernel reads / writes (a consumer's operand may also come from the direct kernel's split-K finish)
+static bool two_axis_io(const s3r_conv_desc* d) {
+    if (d->in_layout == S3R_LAYOUT_WINO_DH || d->in_layout == S3R_LAYOUT_WINO_HW || d->in_layout == S3R_LAYOUT_WINO_3D ||
+        d->out_layout == S3R_LAYOUT_WINO_HW)
+        return true;
+    return d->op == S3R_OP_CONV && (d->out_layout == S3R_LAYOUT_WINO_3D || d->out_layout == S3R_LAYOUT_DIFF) && wino2_ax(d) >= 0 &&
+           !forced_direct(d);
 }
 // library policy: the two-axis form where the output is small enough for its class slabs (ncls / m^2 x the output) to be cheap
 // or, in its semi-fused launch form (6 / 4 x the output), worth the halved matrix work — v1 (edge 28), v3 (14), v5, v6 (7) of this
@@ -398,7 +442,7 @@ int resolve_algo(const s3r_conv_desc* d, int* alg, int* form) {
             return fail(S3R_ERR_INVALID, "algo = WINOGRAD: this layer / descriptor has no such Winograd form (one-axis: fp32 Conv k3 s1 p1 "
                         "with cin %% %d == 0 and edge >= 4, or ConvTranspose3d k4 s2 p1 over an edge %% 4 == 0, in_halo = 1; two-axis "
                         "(tile = 3): Conv3d k3 s1 p1 / k4 s1 p0, in_halo = pad; plain layouts, no split-K, no sigmoid)", s3r::wino_bk());
-        const bool two_io = d->in_layout == S3R_LAYOUT_WINO_DH || d->in_layout == S3R_LAYOUT_WINO_HW || d->out_layout == S3R_LAYOUT_WINO_HW;
+        const bool two_io = two_axis_io(d);
         if (two_io && !(two && (d->tile < 0 || d->tile >= 3)))
             return fail(S3R_ERR_INVALID, "a two-axis transformed input / output runs the two-axis kernel only");
         if (d->tile >= 3 || !one || two_io ||
@@ -408,7 +452,7 @@ int resolve_algo(const s3r_conv_desc* d, int* alg, int* form) {
         } else { *alg = ALG_WINO; *form = d->tile; }
         return S3R_OK;
     }
-    if (d->in_layout == S3R_LAYOUT_WINO_DH || d->in_layout == S3R_LAYOUT_WINO_HW || d->out_layout == S3R_LAYOUT_WINO_HW) {
+    if (two_axis_io(d)) {
         // only the two-axis kernel reads / writes the 36 plane sets
         if (d->algo == S3R_ALGO_DIRECT || !wino2_desc_ok(d) || d->tile >= 0)
             return fail(S3R_ERR_INVALID, "a two-axis transformed input / output runs the two-axis kernel only: algo AUTO / WINOGRAD, no direct "
@@ -423,7 +467,17 @@ int resolve_algo(const s3r_conv_desc* d, int* alg, int* form) {
         *alg = ALG_WINO;
         return S3R_OK;
     }
+    if (d->in_layout == S3R_LAYOUT_DIFF || d->out_layout == S3R_LAYOUT_DIFF) {      // (a transposed layer here: a convolution writing it is two_axis_io)
+        if (d->op != S3R_OP_DECONV || forced_direct(d) || !wino_desc_ok(d))
+            return fail(S3R_ERR_INVALID, "the difference-tensor layout is read / written by the Winograd form of a ConvTranspose3d k4 s2 p1 (algo AUTO / "
+                        "WINOGRAD, no direct tile / split-K override), or written by a two-axis Conv3d");
+        *alg = ALG_WINO;
+        return S3R_OK;
+    }
+    if (d->in_layout == S3R_LAYOUT_WINO_3D || (d->out_layout == S3R_LAYOUT_WINO_3D && d->op != S3R_OP_CONV))
+        return fail(S3R_ERR_INVALID, "the general two-axis layout is read by the two-axis kernel and written by a convolution only");
     if (d->algo == S3R_ALGO_DIRECT || d->tile >= 0 || d->ksplit >= 1 || wino_mode() <= 0) return S3R_OK;
+    if (d->out_layout == S3R_LAYOUT_WINO_3D) return S3R_OK;      // (a convolution without the two-axis form: its split-K finish writes the planes)
     if (wino2_desc_ok(d) && d->in_size <= wino2_max_edge()) *alg = ALG_WINO2;
     // transposed layers with an edge >= 16: the three-axis form (27 / 64 of the multiplications).  r05, d3 (16^3 -> 32^3, fused head)
     // inside the forward: 0.694 -> 0.622 ms at B = 32, -4 % at B = 8 / 16, equal at 4, +5 % at B = 1 / 2 (serial form only: 64
@@ -500,7 +554,7 @@ WinoNeed wino_need(const s3r_conv_desc* d, int form, bool head) {
     if (d->batch <= 0) return w;
     const int kind = wino_kind(d);
     if (d->op == S3R_OP_DECONV) {
-        w.v = dwino_d_elems(d);
+        if (d->in_layout != S3R_LAYOUT_DIFF) w.v = dwino_d_elems(d);
         const int nt = (int)wino_positions(d, d->batch);
         // (form < 0, the library's pick: sized for the class-parallel form, the largest — the pick depends on the device's CU count)
         w.slab = s3r::wino_slab_elems(kind, d->cout, nt, s3r::wino_plan(kind, d->cout, wino_kcls(d), nt, head, form < 0 ? 1 : form));
@@ -539,7 +593,7 @@ WinoNeed wino2_need(const s3r_conv_desc* d, int form) {
     WinoNeed w = {0, 0, 0};
     const Wino2Geo g2 = wino2_geo(d);
     if (d->batch <= 0 || g2.bmax <= 0) return w;
-    if (d->in_layout != S3R_LAYOUT_WINO_DH && d->in_layout != S3R_LAYOUT_WINO_HW)
+    if (d->in_layout != S3R_LAYOUT_WINO_DH && d->in_layout != S3R_LAYOUT_WINO_HW && d->in_layout != S3R_LAYOUT_WINO_3D)
         w.v = ((g2.ax == 2 ? g2.ncls * d->cin * s3r::wino2_npad(g2.pos_sample * g2.bmax) : g2.v_sample * g2.bmax) + 255) / 256 * 256;
     for (int b0 = 0; b0 < d->batch; b0 += g2.bmax) {              // (at most two different sub-batch sizes)
         const int nb = d->batch - b0 < g2.bmax ? d->batch - b0 : g2.bmax;
@@ -784,9 +838,68 @@ int resolve_launch(const s3r_conv_desc* d, s3r::ConvParams* p, Launch* L) {
 
 int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
+// S3R_WINO_HANDOFF (A/B switch, read once): 0 no hand-off at all; unset / 1 all of them; any other value a mask — bit 1 (2) the 2D
+// pair e6 -> e7, bit 2 (4) split-K direct -> two-axis 3D (v4 -> v5), bit 3 (8) two-axis 3D -> two-axis 3D (v5 -> v6), bit 4 (16)
+// two-axis 3D -> transposed (v6 -> d1), bit 5 (32) transposed -> transposed (d1 -> d2)
+static int handoff_mask() {
+    static const int m = getenv("S3R_WINO_HANDOFF") ? atoi(getenv("S3R_WINO_HANDOFF")) : 1;
+    return m == 1 ? ~0 : m;
+}
+
+// 3D hand-off of the pair (a, b) — a's finish pass writing b's operand (s3r_conv_wino.hip, wino_handoff_kernel).  Returns the layout
+// the pair's ALGORITHMS allow (PLAIN: none) — a function of the descriptors alone, which sizes the region — and through *take
+// whether the launch forms planned for this batch on this device take it (both routes give the same bits, so that may follow the
+// batch): the producer must leave whole-range raw sums in slabs (split-K; class-parallel), the consumer's operand must fit one call
+static int handoff3d(const s3r_conv_desc& a, const s3r_conv_desc& b, bool* take) {
+    *take = false;
+    if (a.dtype != S3R_F32 || b.dtype != S3R_F32 || a.ndim != 3 || b.ndim != 3 || a.cout != b.cin || out_size(&a) != b.in_size ||
+        a.batch != b.batch || a.out_halo != b.in_halo || a.act > S3R_ACT_RELU || a.cout % s3r::wino_bk() != 0 || staged_layer(&a) ||
+        staged_layer(&b))
+        return S3R_LAYOUT_PLAIN;
+    const int op = b.in_size + 2 * b.in_halo;
+    if (op * op * op > 8192) return S3R_LAYOUT_PLAIN;                 // (a block of padded volumes in 32 KiB of LDS)
+    int alg_a, form_a, alg_b, form_b;
+    if (resolve_algo(&a, &alg_a, &form_a) != S3R_OK || resolve_algo(&b, &alg_b, &form_b) != S3R_OK) return S3R_LAYOUT_PLAIN;
+    int lay = S3R_LAYOUT_PLAIN, bit = 0;
+    bool forms = true;
+    // (what follows the batch but not the device — one call's worth of planes, materialised differences — decides the layout itself)
+    if (alg_b == ALG_WINO2 && wino2_ax(&b) <= 1 && b.in_halo == b.pad && b.in_size >= (b.pad ? 4 : 5) && wino2_geo(&b).bmax >= b.batch)
+        lay = S3R_LAYOUT_WINO_3D;
+    else if (alg_b == ALG_WINO && b.op == S3R_OP_DECONV && b.in_halo == 1 && dwino_materialise(&b))
+        lay = S3R_LAYOUT_DIFF;
+    else return S3R_LAYOUT_PLAIN;
+    if (alg_a == ALG_WINO2 && wino2_ax(&a) <= 1) {
+        bit = lay == S3R_LAYOUT_DIFF ? 16 : 8;
+        const Wino2Geo g2 = wino2_geo(&a);
+        if (g2.bmax < a.batch) return S3R_LAYOUT_PLAIN;
+        forms = wino2_form_of(&a, (int)(g2.pos_sample * a.batch), form_a) == 0;
+    } else if (alg_a == ALG_WINO && a.op == S3R_OP_DECONV && lay == S3R_LAYOUT_DIFF) {
+        bit = 32;
+        forms = s3r::wino_plan(2, a.cout, wino_kcls(&a), (int)wino_positions(&a, a.batch), false, form_a).mode == s3r::WINO_CP;
+    } else if (alg_a == ALG_DIRECT && a.op == S3R_OP_CONV && lay == S3R_LAYOUT_WINO_3D && a.out_layout == S3R_LAYOUT_PLAIN) {
+        bit = 4;
+        Geo ga;
+        Launch L;
+        if (geometry(&a, &ga) != S3R_OK) return S3R_LAYOUT_PLAIN;
+        s3r::ConvParams pa = make_params(&a, ga);
+        if (resolve_launch(&a, &pa, &L) != S3R_OK || L.ksplit <= 1) return S3R_LAYOUT_PLAIN;      // (split-K follows the per-sample geometry alone)
+    } else return S3R_LAYOUT_PLAIN;
+    if (!(handoff_mask() & bit)) return S3R_LAYOUT_PLAIN;
+    // with the layouts set both layers must still resolve to the algorithms (and forced forms) they have without
+    s3r_conv_desc a2 = a, b2 = b;
+    a2.out_layout = lay; b2.in_layout = lay;
+    int alg2, form2;
+    Geo g2;
+    if (geometry(&a2, &g2) != S3R_OK || geometry(&b2, &g2) != S3R_OK) return S3R_LAYOUT_PLAIN;
+    if (resolve_algo(&a2, &alg2, &form2) != S3R_OK || alg2 != alg_a || form2 != form_a) return S3R_LAYOUT_PLAIN;
+    if (resolve_algo(&b2, &alg2, &form2) != S3R_OK || alg2 != alg_b || form2 != form_b) return S3R_LAYOUT_PLAIN;
+    *take = forms;
+    return lay;
+}
+
 int plan_chain(const s3r_layer* layers, int n, Plan* pl) {
     if (!layers || n <= 0) return fail(S3R_ERR_INVALID, "empty chain");
-    pl->d.resize(n); pl->r.resize(n); pl->g.resize(n); pl->off.assign(n, -1); pl->fuse_head.assign(n, 0);
+    pl->d.resize(n); pl->r.resize(n); pl->g.resize(n); pl->off.assign(n, -1); pl->fuse_head.assign(n, 0); pl->region.assign(n, 0);
     for (int i = 0; i < n; ++i) {
         pl->d[i] = layers[i].desc;
         if (i > 0) pl->d[i].in_layout = S3R_LAYOUT_PLAIN;            // intermediates: the library's plan, not the caller's
@@ -824,7 +937,7 @@ int plan_chain(const s3r_layer* layers, int n, Plan* pl) {
         if (i > 0 && pl->r[i - 1] == R_MFMA && pl->r[i] == R_MFMA && pl->d[i].dtype == S3R_F32) {
             // two-axis Conv2d -> two-axis Conv2d over the same edge: the first one's finish kernel writes the second one's plane sets
             // (S3R_LAYOUT_WINO_HW: the bits wino2p_input_kernel makes of the plain activation)
-            static const int fuse = getenv("S3R_WINO_HANDOFF") ? atoi(getenv("S3R_WINO_HANDOFF")) : 1;      // A/B switch, read once
+            const int fuse = handoff_mask() & 2;
             s3r_conv_desc& a = pl->d[i - 1];
             s3r_conv_desc& b = pl->d[i];
             int alg_a, alg_b, form;
@@ -835,6 +948,23 @@ int plan_chain(const s3r_layer* layers, int n, Plan* pl) {
                 b.in_layout = S3R_LAYOUT_WINO_HW;
                 const int rg = geometry(&a, &pl->g[i - 1]);              // (its output is now the plane sets)
                 if (rg) return rg;
+            }
+            // ... and the small 3D layers: the producer's finish pass writes the consumer's plane sets / difference tensors
+            bool take = false;
+            const int lay = b.ndim == 3 ? handoff3d(a, b, &take) : S3R_LAYOUT_PLAIN;
+            if (lay != S3R_LAYOUT_PLAIN) {
+                s3r_conv_desc a2 = a;
+                a2.out_layout = lay;
+                Geo ga;
+                const int rg = geometry(&a2, &ga);
+                if (rg) return rg;
+                // the region holds either form: its size must not follow the launch forms (they count the device's compute units)
+                pl->region[i - 1] = ga.y_store > pl->g[i - 1].y_store ? ga.y_store : pl->g[i - 1].y_store;
+                if (take) {
+                    a = a2;
+                    b.in_layout = lay;
+                    pl->g[i - 1] = ga;
+                }
             }
         }
         int rc = geometry(&pl->d[i], &pl->g[i]);
@@ -884,10 +1014,14 @@ int plan_chain(const s3r_layer* layers, int n, Plan* pl) {
     for (int i = 0; i + 1 < n; ++i) {
         pl->off[i] = off;
         if (i == 0 && pl->stem_wino) off = align_up(off + pl->g[1].x_store, 256);      // layer 1's transformed planes
-        else if (!pl->fuse_head[i]) off = align_up(off + pl->g[i].y_store, 256);   // a fused conv's output does not exist
+        else if (!pl->fuse_head[i]) off = align_up(off + (pl->region[i] > pl->g[i].y_store ? pl->region[i] : pl->g[i].y_store), 256);   // a fused conv's output does not exist
     }
     for (int i = 0; i < n; ++i) {
-        const int64_t sc = s3r_conv_scratch_elems(&pl->d[i]);
+        // (a 3D hand-off pair is sized for its two-pass route, the larger: the route taken follows the launch forms, the size must not)
+        s3r_conv_desc t = pl->d[i];
+        if (i > 0 && pl->region[i - 1]) t.in_layout = S3R_LAYOUT_PLAIN;
+        if (pl->region[i]) t.out_layout = S3R_LAYOUT_PLAIN;
+        const int64_t sc = s3r_conv_scratch_elems(&t);
         if (sc < 0) return (int)sc;
         if (sc > pl->scratch_elems) pl->scratch_elems = sc;
     }
