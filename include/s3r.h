@@ -14,6 +14,8 @@
  *   s3r_decoder_forward (+conv/deconv/head) the torch conv3d / ConvTranspose3d + BN + ReLU + sigmoid
  *                                           calls of the voxel decoder                  (README.md:77)
  *   s3r_linear_forward                      the point decoder's nn.Linear layers        (README.md:36)
+ *   s3r_linear_backward                     torch autograd's backward of those layers: what `python3 runner.py` (training, the
+ *                                           reference's default mode) runs behind the Chamfer loss   (README.md:36)
  *   s3r_chamfer_forward                     extensions/chamfer_dist (the reference's one native op,
  *                                           built by `python setup.py install`)         (README.md:64-65)
  *   s3r_chamfer_backward                    the backward half of the same extension: the op is usable as a LOSS, with a fixed
@@ -61,7 +63,7 @@ extern "C" {
  * fp32 layers; `tile` = 6 under S3R_ALGO_WINOGRAD names the three-axis form of a transposed convolution (AUTO takes it from edge
  * 16 up: other bits than ABI 7 for such a layer); s3r_profile_detail and record family 10 (aux passes).
  * s3r_disparity_soft and s3r_disparity_metrics were added later as new entry points only (no struct or existing signature changed):
- * the version stays 8.  s3r_chamfer_backward likewise. */
+ * the version stays 8.  s3r_chamfer_backward and s3r_linear_backward (+ its scratch query) likewise. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -305,6 +307,29 @@ int s3r_cost_volume_forward_bf16(const void* feat_left, const void* feat_right, 
 int64_t s3r_linear_scratch_elems(int batch, int cin, int cout);
 int s3r_linear_forward(const float* x, const float* w, const float* bias, float* y, int batch, int cin, int cout,
                        int act, float* scratch, int64_t scratch_elems, void* stream);
+
+/* Backward of s3r_linear_forward's layer y = act(x W^T + bias): x (B,Cin), w (Cout,Cin) torch layout, y and grad_y (B,Cout); grad_x
+ * (B,Cin), grad_w (Cout,Cin), grad_bias (Cout).  act is S3R_ACT_NONE, S3R_ACT_RELU or S3R_ACT_SIGMOID (anything else: S3R_ERR_INVALID).
+ * The pre-activation gradient g (B,Cout) is fp32 with nothing fused:
+ *   none: g = grad_y;   ReLU: g = (y > 0.f) ? grad_y : 0.f (a NaN y gives 0);   sigmoid: t = 1 - y; u = y * t; g = grad_y * u, each
+ *   operation rounded once, in this order.
+ *   grad_bias[o] = sum_b g[b][o]: ONE fp32 accumulator that starts as g[0][o], plain adds in ascending b.  This order IS the contract
+ *                  (bit for bit; with B = 1 it is g itself).
+ *   grad_w[o][i] = sum_b g[b][o] x[b][i]: v_mfma_f32_32x32x2_f32, b ascending inside one workgroup (no split, no scratch).
+ *   grad_x[b][i] = sum_o g[b][o] w[o][i]: the same instruction, o ascending inside a K slice; the slices — a function of (cin, cout)
+ *                  only, never of the device or an address — are written as slabs into `scratch` and added in ascending slice order.
+ * No atomics: the same bits on every run and at every address the alignment rule allows (4 bytes, every argument).
+ * grad_x, grad_w and grad_bias may each be NULL: that output is not computed and costs neither its GEMM nor its traffic (p1 behind a
+ * frozen trunk needs no grad_x: 134 MB of weights not read); the computed ones carry the bits of the full call; all three NULL is
+ * S3R_ERR_INVALID.  x may be NULL when grad_w is, w when grad_x is.  y may be NULL when act is none; y NULL with ReLU or sigmoid is
+ * S3R_ERR_INVALID.  Outputs are overwritten, never accumulated into.  batch, cin, cout > 0; every tensor < 2^31 elements and < 4 GiB.
+ * `scratch` holds g and the slabs: s3r_linear_backward_scratch_elems floats, sized for the worst case over the outputs asked for,
+ * independent of the device, monotone in batch; its contents on entry do not matter; a shorter (or NULL) one is S3R_ERR_WORKSPACE.
+ * Nothing is enqueued when the call is refused.  Profiler: family 4, tag 1; `flops` = 2 batch cin cout per GEMM actually run (grad_w,
+ * grad_x); `bytes` = the tensors the call must read and write (grad_y; y unless act is none; x and grad_w; w and grad_x; grad_bias). */
+int64_t s3r_linear_backward_scratch_elems(int batch, int cin, int cout);
+int s3r_linear_backward(const float* x, const float* w, const float* y, const float* grad_y, float* grad_x, float* grad_w,
+                        float* grad_bias, int batch, int cin, int cout, int act, float* scratch, int64_t scratch_elems, void* stream);
 
 /* squared-L2 nearest neighbours both ways; p (B,N,3), q (B,M,3); dist1, idx1 (B,N): for every point of p its nearest point of q;
  * dist2, idx2 (B,M): the reverse.  The rule, which s3r_chamfer_backward's "same bits for every batch split" rests on:

@@ -875,6 +875,44 @@ int s3r_linear_forward(const float* x, const float* w, const float* bias, float*
     return S3R_OK;
 }
 
+// every tensor of a linear-backward call within the header's limits (< 2^31 elements, < 4 GiB)
+static bool linbwd_too_large(int batch, int cin, int cout) {
+    const int64_t a = (int64_t)batch * cin, b = (int64_t)batch * cout, c = (int64_t)cin * cout;
+    const int64_t m = a > b ? (a > c ? a : c) : (b > c ? b : c);
+    return m >= kMaxElems || 4 * m >= kMaxBytes;
+}
+
+int64_t s3r_linear_backward_scratch_elems(int batch, int cin, int cout) {
+    if (batch <= 0 || cin <= 0 || cout <= 0) return fail(S3R_ERR_INVALID, "linear dims must be positive");
+    if (linbwd_too_large(batch, cin, cout)) return fail(S3R_ERR_INVALID, "tensor of 4 GiB or more: split the batch");
+    return s3r::linear_backward_scratch_elems(batch, cin, cout);
+}
+
+int s3r_linear_backward(const float* x, const float* w, const float* y, const float* grad_y, float* grad_x, float* grad_w,
+                        float* grad_bias, int batch, int cin, int cout, int act, float* scratch, int64_t scratch_elems, void* stream) {
+    if (!grad_x && !grad_w && !grad_bias)
+        return fail(S3R_ERR_INVALID, "linear backward: grad_x, grad_w and grad_bias are all NULL (each may be: it is not computed)");
+    if (act < S3R_ACT_NONE || act > S3R_ACT_SIGMOID)
+        return fail(S3R_ERR_INVALID, "s3r_linear_backward takes none / relu / sigmoid (act %d)", act);
+    if (!grad_y || (grad_w && !x) || (grad_x && !w)) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    if (act != S3R_ACT_NONE && !y) return fail(S3R_ERR_INVALID, "linear backward: y is NULL (it may be only when act is none)");
+    if (batch <= 0 || cin <= 0 || cout <= 0) return fail(S3R_ERR_INVALID, "linear dims must be positive");
+    if (linbwd_too_large(batch, cin, cout)) return fail(S3R_ERR_INVALID, "tensor of 4 GiB or more: split the batch");
+    const int64_t need = s3r::linear_backward_scratch_elems(batch, cin, cout);
+    if (!scratch || scratch_elems < need)
+        return fail(S3R_ERR_WORKSPACE, "linear backward needs %lld floats of scratch (s3r_linear_backward_scratch_elems), got %lld",
+                    (long long)need, (long long)(scratch ? scratch_elems : 0));
+    hipStream_t s = (hipStream_t)stream;
+    const double B = batch, I = cin, O = cout;
+    const double flops = 2.0 * B * I * O * ((grad_w ? 1.0 : 0.0) + (grad_x ? 1.0 : 0.0));
+    const double elems = B * O * (act != S3R_ACT_NONE ? 2.0 : 1.0) + (grad_w ? B * I + I * O : 0.0) + (grad_x ? I * O + B * I : 0.0) +
+                         (grad_bias ? O : 0.0);
+    ProfScope ps(s, F_LINEAR, 1, flops, 4.0 * elems);
+    hipError_t e = s3r::launch_linear_backward(x, w, y, grad_y, grad_x, grad_w, grad_bias, batch, cin, cout, act, scratch, s, &ps.launches);
+    if (e != hipSuccess) return hip_fail(e, "linear backward launch");
+    return S3R_OK;
+}
+
 int s3r_chamfer_forward(const float* p, const float* q, float* dist1, float* dist2, int32_t* idx1, int32_t* idx2,
                         int batch, int n, int m, void* stream) {
     if (!p || !q || !dist1 || !dist2 || !idx1 || !idx2) return fail(S3R_ERR_INVALID, "null tensor pointer");

@@ -280,6 +280,11 @@ hipError_t launch_chamfer_backward(const float* p, const float* q, const int* i1
 hipError_t launch_linear(const float* x, const float* w, const float* scale, const float* bias, float* y, int B,
                          int Cin, int Cout, int act, float* scratch, hipStream_t s);
 int64_t linear_scratch_elems(int B, int Cin, int Cout);
+// s3r_linear_bwd.hip: backward of y = act(x W^T + bias), fixed summation orders, no atomics.  gx, gw, gb: NULL = not computed (not all
+// three); y may be NULL when act is none; scratch: linear_backward_scratch_elems floats (g, then the split-K slabs of grad_x)
+hipError_t launch_linear_backward(const float* x, const float* w, const float* y, const float* gy, float* gx, float* gw, float* gb,
+                                  int B, int Cin, int Cout, int act, float* scratch, hipStream_t s, int* launches);
+int64_t linear_backward_scratch_elems(int B, int Cin, int Cout);
 // ---- bf16 channels-last path
 hipError_t launch_conv_bf16(const ConvParamsH& p, int tm, hipStream_t stream);
 int conv_bf16_pick_tm(const ConvParamsH& p);

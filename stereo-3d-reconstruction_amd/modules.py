@@ -675,6 +675,19 @@ class PointHead(_HipChain):
         x = _check_input(latent, "latent", (spec.LATENT_C, 4, 4, 4))
         return self._run(x.view(x.shape[0], spec.LATENT_C * 64)).view(x.shape[0], spec.N_POINTS, 3)   # (B may be 0)
 
+    def differentiable(self, latent: torch.Tensor) -> torch.Tensor:
+        """`forward` recorded for autograd: the three layers run one by one through `differentiable_linear` on this module's own
+        nn.Linear parameters — the kernel the chain launches for a linear layer, with the same arguments, so the value has the bits
+        of `forward` — and carry the deterministic backward `linear_backward`.  The head of a fine-tune step on a frozen trunk:
+        `ChamferDistance()(head.differentiable(model.latent(l, r)), target).backward()`.  An optimizer's in-place step bumps the
+        parameters' `_version`, which invalidates `forward`'s packed-weight cache."""
+        x = _check_input(latent, "latent", (spec.LATENT_C, 4, 4, 4))
+        h = x.view(x.shape[0], spec.LATENT_C * 64)
+        for l in self._layers:
+            blk: _Block = getattr(self, l.name)
+            h = differentiable_linear(h, blk.conv.weight, blk.conv.bias, l.act)
+        return h.view(x.shape[0], spec.N_POINTS, 3)
+
 
 # Default temperature of the soft read-out (`disparity_soft`, `disparity(readout="soft")`), in units of the matching cost (a sum of
 # C = 32 absolute feature differences).  BUILD-SPECIFIED: no learned disparity head exists to fix it (SURVEY.md §8f row 4).
@@ -817,13 +830,13 @@ class Stereo2Point(_DisparityMixin, nn.Module):
             raise RuntimeError("forward/inference path only")
         return super().train(False)
 
-    @torch.no_grad()
-    def forward(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+    def _latents(self, left: torch.Tensor, right: torch.Tensor):
+        """The trunk — encoder, cost volume, volume encoder — per chunk of MAX_CHUNK pairs: yields the fp32 (b,512,4,4,4) latent.
+        `forward` and `latent` both run THIS, so the two cannot drift apart."""
         left = _check_render(left, "left")
         right = _check_render(right, "right")
         if left.shape[0] != right.shape[0]:
             raise RuntimeError("left and right batch sizes differ")
-        outs = []
         for s in range(0, max(left.shape[0], 1), MAX_CHUNK):
             l, r = left[s:s + MAX_CHUNK], right[s:s + MAX_CHUNK]
             b = l.shape[0]
@@ -832,8 +845,123 @@ class Stereo2Point(_DisparityMixin, nn.Module):
             latent = self.decoder.forward_padded(vol, in_layout=layout)
             if latent.dtype != torch.float32:                      # bf16 channels-last view -> fp32 (B,512,4,4,4): HIP kernel
                 latent = channels_last_to_f32(latent)
-            outs.append(self.point_head(latent))
+            yield latent
+
+    @torch.no_grad()
+    def forward(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+        outs = [self.point_head(latent) for latent in self._latents(left, right)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    @torch.no_grad()
+    def latent(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+        """The frozen trunk alone — encoder, cost volume, volume encoder — without a graph: the fp32 (B,512,4,4,4) latent that
+        `forward` hands to the point head (the same code, the same bits).  `point_head.differentiable(model.latent(l, r))` is the
+        trainable part."""
+        outs = list(self._latents(left, right))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+
+_LINEAR_ACTS = ("none", "relu", "sigmoid")
+
+
+def _check_linear(x, weight, act, who):
+    if act not in _LINEAR_ACTS:
+        raise RuntimeError(f"{who}: act must be one of {_LINEAR_ACTS}, got {act!r}")
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1]:
+        raise RuntimeError(f"{who} expects x (B,Cin) and weight (Cout,Cin), got {tuple(x.shape)} and {tuple(weight.shape)}")
+    x = _check_input(x, "x", (weight.shape[1],))
+    w = weight.detach()
+    if w.device != x.device or w.dtype != torch.float32 or not w.is_contiguous():
+        raise RuntimeError(f"{who}: weight must be a contiguous fp32 tensor on {x.device}")
+    if w.numel() == 0:
+        raise RuntimeError(f"{who} needs a non-empty weight")
+    return x, w
+
+
+@torch.no_grad()
+def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: str = "none") -> torch.Tensor:
+    """act(x weight^T + bias) on the HIP linear kernels (`s3r_linear_forward`): x (B,Cin), weight (Cout,Cin) in torch layout,
+    bias (Cout) or None; act "none", "relu" or "sigmoid".  Records no graph (`differentiable_linear` does)."""
+    x, w = _check_linear(x, weight, act, "linear")
+    B, cin, cout = x.shape[0], w.shape[1], w.shape[0]
+    b = None
+    if bias is not None:
+        b = bias.detach()
+        if b.shape != (cout,) or b.device != x.device or b.dtype != torch.float32 or not b.is_contiguous():
+            raise RuntimeError(f"linear: bias must be a contiguous fp32 ({cout},) tensor on {x.device}")
+    y = torch.empty((B, cout), dtype=torch.float32, device=x.device)
+    if B:
+        lib = _lib.load()
+        need = _lib.check(lib.s3r_linear_scratch_elems(B, cin, cout), "linear scratch query")
+        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+        _lib.check(lib.s3r_linear_forward(x.data_ptr(), w.data_ptr(), None if b is None else b.data_ptr(), y.data_ptr(), B, cin, cout,
+                                          _lib.ACT[act], scratch.data_ptr(), scratch.numel(), _stream_ptr(x.device)), "linear")
+    return y
+
+
+@torch.no_grad()
+def linear_backward(x: torch.Tensor, weight: torch.Tensor, y: Optional[torch.Tensor], grad_y: torch.Tensor, act: str,
+                    need_x: bool = True, need_w: bool = True, need_b: bool = True):
+    """(grad_x (B,Cin), grad_w (Cout,Cin), grad_bias (Cout)) of y = act(x weight^T + bias) for the output gradient grad_y (B,Cout),
+    `None` for the sides not asked for (`s3r_linear_backward`).  y is the layer's output (it may be None when act is "none").  Fixed
+    summation orders, no atomics: the same bits on every run.  A side that is not needed costs neither its GEMM nor its traffic."""
+    x, w = _check_linear(x, weight, act, "linear_backward")
+    if not (need_x or need_w or need_b):
+        raise RuntimeError("linear_backward needs need_x, need_w or need_b")
+    B, cin, cout = x.shape[0], w.shape[1], w.shape[0]
+    gy = _check_input(grad_y, "grad_y", (cout,))
+    if gy.shape[0] != B:
+        raise RuntimeError(f"grad_y must have batch {B}, got {tuple(gy.shape)}")
+    yy = None
+    if act != "none":
+        if y is None:
+            raise RuntimeError(f"linear_backward: act {act!r} needs the layer's output y")
+        yy = _check_input(y, "y", (cout,))
+        if yy.shape[0] != B:
+            raise RuntimeError(f"y must have batch {B}, got {tuple(yy.shape)}")
+    dev = x.device
+    gx = torch.empty((B, cin), dtype=torch.float32, device=dev) if need_x else None
+    gw = torch.empty((cout, cin), dtype=torch.float32, device=dev) if need_w else None
+    gb = torch.empty((cout,), dtype=torch.float32, device=dev) if need_b else None
+    if B == 0:                                     # an empty sum
+        for t in (gw, gb):
+            if t is not None:
+                t.zero_()
+        return gx, gw, gb
+    lib = _lib.load()
+    need = _lib.check(lib.s3r_linear_backward_scratch_elems(B, cin, cout), "linear backward scratch query")
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    ptr = [None if t is None else t.data_ptr() for t in (yy, gy, gx, gw, gb)]
+    _lib.check(lib.s3r_linear_backward(x.data_ptr(), w.data_ptr(), *ptr, B, cin, cout, _lib.ACT[act], scratch.data_ptr(),
+                                       scratch.numel(), _stream_ptr(dev)), "linear backward")
+    return gx, gw, gb
+
+
+class _LinearFunction(torch.autograd.Function):
+    """`linear` with `linear_backward` as its derivative; saves x, weight and y"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act):
+        y = linear(x, weight, bias, act)
+        ctx.act = act
+        ctx.save_for_backward(x, weight, y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, weight, y = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        if not (need_x or need_w or need_b):
+            return None, None, None, None
+        gx, gw, gb = linear_backward(x, weight, y, grad_y.contiguous().float(), ctx.act, need_x, need_w, need_b)
+        return gx, gw, gb, None
+
+
+def differentiable_linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: str = "none") -> torch.Tensor:
+    """`linear` recorded for autograd: the same bits, with the deterministic backward `linear_backward`, called with exactly the
+    sides autograd needs (`needs_input_grad`).  A B = 0 input gives zero gradients without a kernel call."""
+    return _LinearFunction.apply(x, weight, bias, act)
 
 
 @torch.no_grad()
