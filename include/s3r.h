@@ -21,6 +21,11 @@
  *   s3r_chamfer_backward                    the backward half of the same extension: the op is usable as a LOSS, with a fixed
  *                                           summation order instead of the usual atomicAdd scatter   (README.md:64-65)
  *   s3r_voxel_iou                           the IoU metric of `runner.py --test`        (README.md:88-92)
+ *   s3r_voxel_bce_forward / _backward       torch.nn.BCELoss on the sigmoid occupancy grid and its autograd backward: the loss the
+ *                                           reference family trains voxel grids with (`python3 runner.py`), with a fixed summation
+ *                                           order                                       (README.md:77)
+ *   s3r_head_backward                       torch autograd's backward of the occupancy head's conv3d(64 -> 1, k = 1) + bias + sigmoid:
+ *                                           one pass over the grid, fixed summation orders, no atomics   (README.md:77)
  *   s3r_disparity_wta, s3r_disparity_epe    predicted left / right disparity and its end-point error
  *                                           against the disp_%02d_{l,r}.exr ground truth (README.md:75-76)
  *   s3r_disparity_soft                      the same prediction as a sub-pixel soft-argmin, upsampled to the
@@ -63,7 +68,8 @@ extern "C" {
  * fp32 layers; `tile` = 6 under S3R_ALGO_WINOGRAD names the three-axis form of a transposed convolution (AUTO takes it from edge
  * 16 up: other bits than ABI 7 for such a layer); s3r_profile_detail and record family 10 (aux passes).
  * s3r_disparity_soft and s3r_disparity_metrics were added later as new entry points only (no struct or existing signature changed):
- * the version stays 8.  s3r_chamfer_backward and s3r_linear_backward (+ its scratch query) likewise. */
+ * the version stays 8.  s3r_chamfer_backward and s3r_linear_backward (+ its scratch query) likewise; s3r_voxel_bce_forward,
+ * s3r_voxel_bce_backward and s3r_head_backward (+ its scratch query) likewise. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -377,6 +383,76 @@ int s3r_chamfer_backward(const float* p, const float* q, const int32_t* idx1, co
 int s3r_voxel_iou(const float* pred, const float* gt, float threshold, float* iou, int batch, int64_t voxels,
                   void* stream);
 
+/* Binary cross-entropy of an occupancy grid: torch.nn.BCELoss's per-element rule with a per-sample sum.  pred and target are (B, V)
+ * fp32; target may be soft (any value in [0, 1]).  Per element, fp32, every operation rounded once, nothing fused:
+ *   a = clamp(logf(p));  c = clamp(logf(1.f - p));  l = -(t * a + (1.f - t) * c);  clamp(v) = (v < -100.f) ? -100.f : v
+ * logf is the device math library's (not correctly rounded: l is within a few ulp of the real value, not a bit-for-bit contract; the
+ * sum's ORDER below is).  The clamp comes BEFORE the multiplication, so p = 0, t = 0 gives 0 and not 0 * -inf = NaN: p == 0, t == 1
+ * gives exactly 100; p == 1, t == 0 gives exactly 100; p == t at either end gives 0.  The clamp is a compare-and-select, so a NaN
+ * passes through it (fmaxf would swallow it): a NaN or out-of-range pred (p < 0 or p > 1) makes that element's l, and with it that
+ * sample's loss_sum, NaN — that sample only, and it is not an error (torch.nn.BCELoss raises on an out-of-range input; this entry
+ * never reads its inputs on the host).
+ * loss_sum (B): the fp32 sum of the sample's V losses in a fixed order that is a function of V only — never of B, the device's
+ * compute-unit count or an address — so sample b has the same bits in every batch split.  The order, which IS the contract:
+ *   - the V losses are cut into chunks of 1024 consecutive elements (the last may be short; missing elements count as +0.0);
+ *   - within a chunk, lane L (0..63) owns the 16 elements 256 j + 4 L + i (j = 0..3, i = 0..3) and adds them in ascending element
+ *     order to a partial that starts as +0.0; the 64 partials are combined by the halving tree v[L] = v[L] + v[L + o] for L < o,
+ *     o = 32, 16, 8, 4, 2, 1; v[0] is the chunk's sum;
+ *   - the chunk sums are added in ascending chunk order into one accumulator that starts as chunk 0's sum.
+ * loss_elem (B, V) may be NULL; otherwise it receives every l, and passing it does not change loss_sum's bits.  loss_sum may be NULL
+ * when loss_elem is not; both NULL is S3R_ERR_INVALID.  One kernel launch, one workgroup per sample, no atomics, no scratch.
+ * batch >= 0 (0 launches nothing and returns S3R_OK), voxels > 0, the tensors < 2^31 elements and < 4 GiB; pred and target non-NULL;
+ * 4-byte alignment for every argument, the same bits at every address.  Outputs are overwritten.  Nothing is enqueued when the call is
+ * refused.  Profiler: family 6, tag 1; `bytes` = pred, target, loss_elem when given, loss_sum when given. */
+int s3r_voxel_bce_forward(const float* pred, const float* target, float* loss_sum, float* loss_elem, int batch, int64_t voxels,
+                          void* stream);
+
+/* Gradient of sum_b grad_scale[b] * loss_sum[b] with respect to pred: grad_pred (B, V), grad_scale (B); for the mean over all B V
+ * elements a caller passes grad_output / (B V) in every grad_scale[b].  Per element, fp32, each operation rounded once, in this order:
+ *   n = grad_scale[b] * (p - t);  d = max((1.f - p) * p, 1e-12f);  grad_pred = n / d      (the division is IEEE-correct)
+ * which is torch's binary_cross_entropy_backward with its epsilon: elementwise, so bit for bit against a restatement.  A NaN pred gives
+ * a NaN gradient in that element only.  All four pointers non-NULL; dims, limits, alignment and batch == 0 as the forward.  One kernel
+ * launch.  Profiler: family 6, tag 2; `bytes` = pred, target, grad_pred and grad_scale. */
+int s3r_voxel_bce_backward(const float* pred, const float* target, const float* grad_scale, float* grad_pred, int batch,
+                           int64_t voxels, void* stream);
+
+/* Backward of the pointwise head that s3r_conv_forward runs for Conv(C -> 1, k = 1) + affine + activation (the occupancy head d4):
+ *   y[b][s] = act(fmaf(sum_c x[b][c][s] w[c], scale, shift))
+ * x (B,C,S), w (C), scale ONE float or NULL for 1 (frozen: it gets no gradient), y and grad_y (B,S); grad_x (B,C,S), grad_w (C),
+ * grad_shift (1).  Any S >= 1, not only multiples of 4.  act is S3R_ACT_NONE, S3R_ACT_RELU or S3R_ACT_SIGMOID (anything else:
+ * S3R_ERR_INVALID).
+ * The pre-activation gradient g (B,S) is fp32 with nothing fused:
+ *   none: g = grad_y;   ReLU: g = (y > 0.f) ? grad_y : 0.f (a NaN y gives 0);   sigmoid: t = 1 - y; u = y * t; g = grad_y * u, each
+ *   operation rounded once, in this order.
+ *   gs = g * scale, rounded once; g itself when scale is NULL.
+ *   grad_x[b][c][s] = gs[b][s] * w[c]: one multiplication (bit for bit).
+ *   grad_w[c]  = sum_{b,s} gs[b][s] x[b][c][s]      grad_shift = sum_{b,s} g[b][s]
+ * Summation order of grad_w[c] and grad_shift, which IS the contract (bit for bit):
+ *   - a sample's S positions are cut into chunks of 512 consecutive positions (the last may be short; missing positions count as +0.0);
+ *   - within a chunk, lane L (0..63) owns the 8 positions 256 j + 4 L + i (j = 0, 1; i = 0..3) and walks them in ascending position
+ *     with a partial that starts as +0.0: grad_w takes partial = partial + gs * x — the product is rounded, then the add: they
+ *     are NOT fused —, grad_shift takes partial = partial + g; the 64 partials are combined by the halving tree
+ *     v[L] = v[L] + v[L + o] for L < o, o = 32, 16, 8, 4, 2, 1; v[0] is the chunk's sum;
+ *   - per sample, the chunk sums are added in ascending chunk order into a partial that starts as chunk 0's sum: a function of S only;
+ *   - the per-sample partials are added into one accumulator in ascending b, starting from sample 0's.
+ * The chunk sums go through `scratch`.  No atomics: the same bits on every run and at every address the alignment rule allows (4 bytes,
+ * every argument; a sample's result does not depend on the batch it is in, only the final ascending-b sum does).
+ * grad_x, grad_w and grad_shift may each be NULL: that output is not computed — grad_x NULL does not cost its write (268 MB at B = 32),
+ * grad_w NULL does not cost the read of x; the computed ones carry the bits of the full call; all three NULL is S3R_ERR_INVALID.  x may
+ * be NULL when grad_w is, w when grad_x is.  y may be NULL when act is none; y NULL with ReLU or sigmoid is S3R_ERR_INVALID.  Outputs
+ * are overwritten, never accumulated into.  batch >= 0 (0 launches nothing, writes nothing and returns S3R_OK), channels, voxels > 0;
+ * every tensor < 2^31 elements and < 4 GiB.
+ * `scratch` holds the chunk sums: s3r_head_backward_scratch_elems floats ((channels + 1) * batch * ceil(voxels / 512)), sized for the
+ * worst case over the outputs asked for, independent of the device, monotone in batch; its contents on entry do not matter; a shorter
+ * (or NULL) one is S3R_ERR_WORKSPACE.  Nothing is enqueued when the call is refused.  One streaming launch plus one finish launch (none
+ * for grad_x alone).  Profiler: family 2, tag 1; `flops` = 2 batch channels voxels for grad_w + batch channels voxels for grad_x;
+ * `bytes` = the tensors the call must read and write (grad_y; y unless act is none; scale when given; x and grad_w; w and grad_x;
+ * grad_shift). */
+int64_t s3r_head_backward_scratch_elems(int batch, int channels, int64_t voxels);
+int s3r_head_backward(const float* x, const float* w, const float* scale, const float* y, const float* grad_y, float* grad_x,
+                      float* grad_w, float* grad_shift, int batch, int channels, int64_t voxels, int act, float* scratch,
+                      int64_t scratch_elems, void* stream);
+
 /* Disparity read-out: winner-take-all over the shift-and-diff costs of the cost volume (same features, same
  * |L - R shifted| costs, volume never materialised).  feat_* (B,C,H,W) fp32; disp_* (B,H,W) fp32, integer-valued,
  * in feature-resolution pixels:
@@ -415,7 +491,7 @@ int s3r_disparity_metrics(const float* pred, const float* gt, float* epe, int32_
 
 /* Kernel-level profiler: when enabled, every kernel the library launches is bracketed by HIP events
  * on the launch stream.  s3r_profile_read synchronises those events and returns, per launch, the
- * kernel family (0 mfma conv, 1 stem, 2 head, 3 cost volume, 4 linear, 5 chamfer, 6 iou, 7 pack, 8 pad copy, 9 disparity read-out / epe,
+ * kernel family (0 mfma conv, 1 stem, 2 head (tag 1: its backward), 3 cost volume, 4 linear, 5 chamfer, 6 iou (tags 1, 2: voxel BCE), 7 pack, 8 pad copy, 9 disparity read-out / epe,
  * 10 aux: ONE transform / difference / finish / split-K-combine pass of a convolution layer — no matrix work, `bytes` = what it must
  * read and write — recorded INSIDE that layer's family-0 record, same tag: the layer's record includes its aux passes' time),
  * the caller's tag, milliseconds, and the algorithmic flops / bytes of that launch. */

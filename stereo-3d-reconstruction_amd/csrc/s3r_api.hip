@@ -957,6 +957,88 @@ int s3r_voxel_iou(const float* pred, const float* gt, float threshold, float* io
     return S3R_OK;
 }
 
+// (B V) of a BCE call within the header's limits (< 2^31 elements, < 4 GiB)
+static int bce_dims(int batch, int64_t voxels) {
+    if (batch < 0 || voxels <= 0) return fail(S3R_ERR_INVALID, "voxel BCE dims: batch >= 0 and voxels > 0 (batch %d, voxels %lld)", batch, (long long)voxels);
+    if (voxels >= kMaxElems || (int64_t)batch * voxels >= kMaxElems || 4 * (int64_t)batch * voxels >= kMaxBytes)
+        return fail(S3R_ERR_INVALID, "tensor of 4 GiB or more: split the batch");
+    return S3R_OK;
+}
+
+int s3r_voxel_bce_forward(const float* pred, const float* target, float* loss_sum, float* loss_elem, int batch, int64_t voxels,
+                          void* stream) {
+    if (!loss_sum && !loss_elem)
+        return fail(S3R_ERR_INVALID, "voxel BCE: loss_sum and loss_elem are both NULL (one may be: it is not written)");
+    int rc = bce_dims(batch, voxels);
+    if (rc) return rc;
+    if (batch == 0) return S3R_OK;
+    if (!pred || !target) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    hipStream_t s = (hipStream_t)stream;
+    const double n = (double)batch * (double)voxels;
+    ProfScope ps(s, F_IOU, 1, 0.0, 4.0 * (n * (loss_elem ? 3.0 : 2.0) + (loss_sum ? batch : 0)));
+    hipError_t e = s3r::launch_voxel_bce(pred, target, loss_sum, loss_elem, batch, voxels, s);
+    if (e != hipSuccess) return hip_fail(e, "voxel BCE launch");
+    return S3R_OK;
+}
+
+int s3r_voxel_bce_backward(const float* pred, const float* target, const float* grad_scale, float* grad_pred, int batch,
+                           int64_t voxels, void* stream) {
+    int rc = bce_dims(batch, voxels);
+    if (rc) return rc;
+    if (batch == 0) return S3R_OK;
+    if (!pred || !target || !grad_scale || !grad_pred) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope ps(s, F_IOU, 2, 0.0, 4.0 * (3.0 * batch * (double)voxels + batch));
+    hipError_t e = s3r::launch_voxel_bce_backward(pred, target, grad_scale, grad_pred, batch, voxels, s);
+    if (e != hipSuccess) return hip_fail(e, "voxel BCE backward launch");
+    return S3R_OK;
+}
+
+// x / grad_x of a head-backward call within the header's limits (< 2^31 elements, < 4 GiB); they are its largest tensors
+static int headbwd_dims(int batch, int channels, int64_t voxels) {
+    if (batch < 0 || channels <= 0 || voxels <= 0)
+        return fail(S3R_ERR_INVALID, "head backward dims: batch >= 0, channels > 0 and voxels > 0 (batch %d, channels %d, voxels %lld)", batch,
+                    channels, (long long)voxels);
+    if (voxels >= kMaxElems || (int64_t)channels * voxels >= kMaxElems || (int64_t)batch * channels * voxels >= kMaxElems ||
+        4 * (int64_t)batch * channels * voxels >= kMaxBytes)
+        return fail(S3R_ERR_INVALID, "tensor of 4 GiB or more: split the batch");
+    return S3R_OK;
+}
+
+int64_t s3r_head_backward_scratch_elems(int batch, int channels, int64_t voxels) {
+    int rc = headbwd_dims(batch, channels, voxels);
+    if (rc) return rc;
+    return s3r::head_backward_scratch_elems(batch, channels, voxels);
+}
+
+int s3r_head_backward(const float* x, const float* w, const float* scale, const float* y, const float* grad_y, float* grad_x,
+                      float* grad_w, float* grad_shift, int batch, int channels, int64_t voxels, int act, float* scratch,
+                      int64_t scratch_elems, void* stream) {
+    if (!grad_x && !grad_w && !grad_shift)
+        return fail(S3R_ERR_INVALID, "head backward: grad_x, grad_w and grad_shift are all NULL (each may be: it is not computed)");
+    if (act < S3R_ACT_NONE || act > S3R_ACT_SIGMOID)
+        return fail(S3R_ERR_INVALID, "s3r_head_backward takes none / relu / sigmoid (act %d)", act);
+    int rc = headbwd_dims(batch, channels, voxels);
+    if (rc) return rc;
+    if (batch == 0) return S3R_OK;
+    if (!grad_y || (grad_w && !x) || (grad_x && !w)) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    if (act != S3R_ACT_NONE && !y) return fail(S3R_ERR_INVALID, "head backward: y is NULL (it may be only when act is none)");
+    const int64_t need = s3r::head_backward_scratch_elems(batch, channels, voxels);
+    if (!scratch || scratch_elems < need)
+        return fail(S3R_ERR_WORKSPACE, "head backward needs %lld floats of scratch (s3r_head_backward_scratch_elems), got %lld",
+                    (long long)need, (long long)(scratch ? scratch_elems : 0));
+    hipStream_t s = (hipStream_t)stream;
+    const double B = batch, C = channels, S = (double)voxels;
+    const double flops = (grad_w ? 2.0 * B * C * S : 0.0) + (grad_x ? B * C * S : 0.0);
+    const double elems = B * S * (act != S3R_ACT_NONE ? 2.0 : 1.0) + (scale ? 1.0 : 0.0) + (grad_w ? B * C * S + C : 0.0) +
+                         (grad_x ? C + B * C * S : 0.0) + (grad_shift ? 1.0 : 0.0);
+    ProfScope ps(s, F_HEAD, 1, flops, 4.0 * elems);
+    hipError_t e = s3r::launch_head_backward(x, w, scale, y, grad_y, grad_x, grad_w, grad_shift, batch, channels, voxels, act, scratch, s,
+                                             &ps.launches);
+    if (e != hipSuccess) return hip_fail(e, "head backward launch");
+    return S3R_OK;
+}
+
 int s3r_disparity_wta(const float* feat_l, const float* feat_r, float* disp_l, float* disp_r, int batch, int channels,
                       int height, int width, int max_disp, void* stream) {
     if (!feat_l || !feat_r || !disp_l || !disp_r) return fail(S3R_ERR_INVALID, "null tensor pointer");

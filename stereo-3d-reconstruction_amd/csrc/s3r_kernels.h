@@ -285,6 +285,18 @@ int64_t linear_scratch_elems(int B, int Cin, int Cout);
 hipError_t launch_linear_backward(const float* x, const float* w, const float* y, const float* gy, float* gx, float* gw, float* gb,
                                   int B, int Cin, int Cout, int act, float* scratch, hipStream_t s, int* launches);
 int64_t linear_backward_scratch_elems(int B, int Cin, int Cout);
+// s3r_head_bwd.hip: backward of the pointwise head y = act(fmaf(sum_c x w, scale, shift)), fixed summation orders, no atomics.  gx, gw,
+// gshift: NULL = not computed (not all three); scratch: head_backward_scratch_elems floats of chunk sums
+hipError_t launch_head_backward(const float* x, const float* w, const float* scale, const float* y, const float* gy, float* gx,
+                                float* gw, float* gshift, int B, int C, int64_t S, int act, float* scratch, hipStream_t s,
+                                int* launches);
+int64_t head_backward_scratch_elems(int B, int C, int64_t S);
+// s3r_voxel_loss.hip: BCELoss's per-element rule with a per-sample sum in a fixed order (loss_sum or loss_elem may be NULL), and its
+// elementwise gradient
+hipError_t launch_voxel_bce(const float* pred, const float* target, float* loss_sum, float* loss_elem, int B, int64_t V,
+                            hipStream_t s);
+hipError_t launch_voxel_bce_backward(const float* pred, const float* target, const float* gscale, float* gpred, int B, int64_t V,
+                                     hipStream_t s);
 // ---- bf16 channels-last path
 hipError_t launch_conv_bf16(const ConvParamsH& p, int tm, hipStream_t stream);
 int conv_bf16_pick_tm(const ConvParamsH& p);

@@ -628,17 +628,46 @@ class Decoder(_HipChain):
         y = self._run(x, upto)
         return y.squeeze(1) if upto is None or upto == self.names[-1] else y
 
-    def forward_padded(self, volume_padded: torch.Tensor, halo: int = 1, in_layout: int = 0) -> torch.Tensor:
+    def forward_padded(self, volume_padded: torch.Tensor, halo: int = 1, in_layout: int = 0, upto: Optional[str] = None) -> torch.Tensor:
         """Decoder on the halo-padded volume CostVolume.forward_padded produced (no pad copy), or (in_layout =
         LAYOUT_WINO_H) on the transformed planes CostVolume.forward_wino produced."""
+        last = upto is None or upto == self.names[-1]
         if in_layout in (_lib.LAYOUT_WINO_H, _lib.LAYOUT_WINO_DH):
-            return self._run(_check_wino_planes(volume_padded, in_layout), None, in_halo=1, in_layout=in_layout).squeeze(1)
+            y = self._run(_check_wino_planes(volume_padded, in_layout), upto, in_halo=1, in_layout=in_layout)
+            return y.squeeze(1) if last else y
         n = (spec.MAX_DISP + 2 * halo, spec.FEAT_HW + 2 * halo, spec.FEAT_HW + 2 * halo)
         if self.precision == "bf16":
             x = _check_input(volume_padded, "volume_padded", n + (2 * spec.FEAT_C,), torch.bfloat16)
         else:
             x = _check_input(volume_padded, "volume_padded", (2 * spec.FEAT_C,) + n)
-        return self._run(x, None, in_halo=halo).squeeze(1)
+        y = self._run(x, upto, in_halo=halo)
+        return y.squeeze(1) if last else y
+
+    # -- the trainable occupancy head (fp32 models) ---------------------------------------------------
+    FEATURES = "d3"          # the layer whose output the occupancy head reads
+
+    def _fp32_only(self, what: str):
+        if self.precision != "fp32":
+            raise RuntimeError(f"{what} is implemented for fp32 models only (this one is {self.precision}): the head backward and the "
+                               "BCE kernels read fp32 tensors")
+
+    def features(self, volume: torch.Tensor) -> torch.Tensor:
+        """`forward(volume, upto="d3")`: the (B,64,32,32,32) activation the occupancy head reads, without a graph.  `forward`
+        fuses d4 into d3's finish kernel, so this tensor exists only here."""
+        self._fp32_only("Decoder.features")
+        return self.forward(volume, upto=self.FEATURES)
+
+    def differentiable_head(self, features: torch.Tensor) -> torch.Tensor:
+        """The occupancy head d4 alone, recorded for autograd on d4's own nn.Conv3d parameters (the weight viewed as (64), gradients
+        returned in the parameters' shapes): (B,64,32,32,32) -> (B,32,32,32).  The value is the STANDALONE head kernel's
+        (`differentiable_head` below); `forward` computes d4 inside d3's finish pass, which agrees to fp32 rounding, not by contract
+        bit for bit.  The head of a fine-tune step on a frozen trunk:
+        `VoxelBCELoss()(model.decoder.differentiable_head(model.head_features(l, r)), gt).backward()`."""
+        self._fp32_only("Decoder.differentiable_head")
+        l = self._layers[-1]
+        x = _check_input(features, "features", (l.cin,) + (spec.VOX,) * 3)
+        blk: _Block = getattr(self, l.name)
+        return differentiable_head(x, blk.conv.weight, blk.conv.bias, l.act)
 
 
 class VolumeEncoder(_HipChain):
@@ -779,21 +808,34 @@ class Stereo2Voxel(_DisparityMixin, nn.Module):
             raise RuntimeError("forward/inference path only")
         return super().train(False)
 
-    @torch.no_grad()
-    def forward(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
-        """left, right: (B,3,224,224) float32 in [0,1] or uint8 (8-bit renders: scaled by 1/255 inside the first kernel)."""
+    def _decoded(self, left: torch.Tensor, right: torch.Tensor, upto: Optional[str] = None):
+        """Encoder, cost volume and the decoder up to `upto` (None: all of it) per chunk of MAX_CHUNK pairs.  `forward` and
+        `head_features` both run THIS, so the two cannot drift apart."""
         left = _check_render(left, "left")
         right = _check_render(right, "right")
         if left.shape[0] != right.shape[0]:
             raise RuntimeError("left and right batch sizes differ")
-        outs = []
         for s in range(0, max(left.shape[0], 1), MAX_CHUNK):
             l, r = left[s:s + MAX_CHUNK], right[s:s + MAX_CHUNK]
             b = l.shape[0]
             feats = self.encoder.forward_pair(l, r)          # (2b,32,28,28): left batch, then right batch
             # (v1 on a Winograd kernel: the volume goes over in the transformed layout that kernel reads)
             vol, layout = self.cost_volume.forward_for(self.decoder, feats[:b], feats[b:])
-            outs.append(self.decoder.forward_padded(vol, in_layout=layout))
+            yield self.decoder.forward_padded(vol, in_layout=layout, upto=upto)
+
+    @torch.no_grad()
+    def forward(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+        """left, right: (B,3,224,224) float32 in [0,1] or uint8 (8-bit renders: scaled by 1/255 inside the first kernel)."""
+        outs = list(self._decoded(left, right))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    @torch.no_grad()
+    def head_features(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
+        """The frozen trunk alone — encoder, cost volume, decoder up to d3 — without a graph: the fp32 (B,64,32,32,32) activation the
+        occupancy head reads (the counterpart of `Stereo2Point.latent`).  `decoder.differentiable_head(model.head_features(l, r))`
+        is the trainable part.  fp32 models only."""
+        self.decoder._fp32_only("Stereo2Voxel.head_features")
+        outs = list(self._decoded(left, right, upto=Decoder.FEATURES))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
     @torch.no_grad()
@@ -1065,6 +1107,217 @@ class ChamferDistance(nn.Module):
         else:
             d1, d2, _, _ = chamfer_distance(p, q)
         return d1.mean() + d2.mean()
+
+
+def _check_bce(pred, target, who):
+    if not isinstance(pred, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise TypeError(f"{who}: pred and target must be torch.Tensors")
+    if pred.dim() < 2 or pred.shape != target.shape:
+        raise RuntimeError(f"{who} expects pred and target of one shape (B, ...), got {tuple(pred.shape)} and {tuple(target.shape)}")
+    p = _check_input(pred.detach(), "pred", pred.shape[1:])
+    t = _check_input(target.detach(), "target", target.shape[1:])
+    voxels = 1
+    for n in pred.shape[1:]:
+        voxels *= n
+    if voxels == 0:
+        raise RuntimeError(f"{who} needs non-empty samples")
+    return p, t, pred.shape[0], voxels
+
+
+@torch.no_grad()
+def voxel_bce(pred: torch.Tensor, target: torch.Tensor, elements: bool = False):
+    """(loss_sum (B), loss_elem or None) of torch.nn.BCELoss's per-element rule on pred, target (B, ...) (`s3r_voxel_bce_forward`):
+    l = -(t * clamp(log p) + (1 - t) * clamp(log(1 - p))), the logs clamped at -100 before the multiplication; loss_sum[b] is the fp32
+    sum of sample b's losses in a fixed order that depends on the sample size only (include/s3r.h), so it has the same bits in every
+    batch split; loss_elem (the shape of pred) is returned with `elements=True`.  A NaN or out-of-range pred makes that sample's sum
+    NaN (torch raises instead).  Records no graph (`differentiable_voxel_bce` does)."""
+    p, t, B, V = _check_bce(pred, target, "voxel_bce")
+    s = torch.empty((B,), dtype=torch.float32, device=p.device)
+    e = torch.empty(p.shape, dtype=torch.float32, device=p.device) if elements else None
+    if B:
+        _lib.check(_lib.load().s3r_voxel_bce_forward(p.data_ptr(), t.data_ptr(), s.data_ptr(), None if e is None else e.data_ptr(), B, V,
+                                                     _stream_ptr(p.device)), "voxel_bce")
+    return s, e
+
+
+@torch.no_grad()
+def voxel_bce_backward(pred: torch.Tensor, target: torch.Tensor, grad_scale: torch.Tensor) -> torch.Tensor:
+    """grad_pred (the shape of pred) of sum_b grad_scale[b] * loss_sum[b] (`s3r_voxel_bce_backward`): grad_scale[b] * (p - t) /
+    max((1 - p) * p, 1e-12), each operation rounded once — torch's binary_cross_entropy_backward, elementwise and bit for bit."""
+    p, t, B, V = _check_bce(pred, target, "voxel_bce_backward")
+    gs = _check_input(grad_scale, "grad_scale", ())
+    if gs.shape[0] != B:
+        raise RuntimeError(f"grad_scale must have shape ({B},), got {tuple(gs.shape)}")
+    g = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+    if B:
+        _lib.check(_lib.load().s3r_voxel_bce_backward(p.data_ptr(), t.data_ptr(), gs.data_ptr(), g.data_ptr(), B, V, _stream_ptr(p.device)),
+                   "voxel_bce backward")
+    return g
+
+
+class _VoxelBCEFunction(torch.autograd.Function):
+    """`voxel_bce`'s loss_sum with `voxel_bce_backward` as its derivative; the gradient goes to pred only"""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        s, _ = voxel_bce(pred, target)
+        ctx.save_for_backward(pred, target)
+        return s
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_sum):
+        pred, target = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        return voxel_bce_backward(pred, target, grad_sum.contiguous().float()), None
+
+
+def differentiable_voxel_bce(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """`voxel_bce`'s loss_sum (B) recorded for autograd: the same bits, with the elementwise backward `voxel_bce_backward`.  The
+    gradient goes to pred only (a target is a constant of the loss)."""
+    return _VoxelBCEFunction.apply(pred, target)
+
+
+class VoxelBCELoss(nn.Module):
+    """torch.nn.BCELoss (mean reduction) on occupancy grids: forward(pred, target) with pred, target (B,32,32,32) or any (B, ...)
+    returns the mean over all elements, `loss_sum.double().sum() / (B V)` cast to fp32 — the per-sample sums are the HIP kernel's,
+    in its fixed order.  With grad mode on and pred requiring grad the value (the same bits) is recorded for autograd through
+    `differentiable_voxel_bce`; otherwise nothing is recorded (as `ChamferDistance`)."""
+
+    def forward(self, pred, target):
+        if torch.is_grad_enabled() and pred.requires_grad:
+            s = differentiable_voxel_bce(pred, target)
+        else:
+            s, _ = voxel_bce(pred, target)
+        return (s.double().sum() / max(pred.numel(), 1)).float()
+
+
+def _check_head(x, weight, act, who):
+    if act not in _LINEAR_ACTS:
+        raise RuntimeError(f"{who}: act must be one of {_LINEAR_ACTS}, got {act!r}")
+    if not isinstance(x, torch.Tensor) or x.dim() < 3:
+        raise RuntimeError(f"{who} expects x (B, C, ...), got {tuple(getattr(x, 'shape', ()))}")
+    if weight.numel() != x.shape[1]:
+        raise RuntimeError(f"{who} expects a weight of {x.shape[1]} elements (Conv(C -> 1, k = 1)), got {tuple(weight.shape)}")
+    x = _check_input(x.detach(), "x", x.shape[1:])
+    w = weight.detach()
+    if w.device != x.device or w.dtype != torch.float32 or not w.is_contiguous():
+        raise RuntimeError(f"{who}: weight must be a contiguous fp32 tensor on {x.device}")
+    positions = 1
+    for n in x.shape[2:]:
+        positions *= n
+    if x.shape[1] == 0 or positions == 0:
+        raise RuntimeError(f"{who} needs non-empty channels and positions")
+    return x, w.view(-1), positions
+
+
+def _check_head_bias(bias, device, who):
+    if bias is None:
+        return None
+    b = bias.detach()
+    if b.numel() != 1 or b.device != device or b.dtype != torch.float32:
+        raise RuntimeError(f"{who}: bias must be one fp32 element on {device}")
+    return b.reshape(1)
+
+
+@torch.no_grad()
+def head(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: str = "sigmoid") -> torch.Tensor:
+    """The pointwise head act(sum_c x[:, c] weight[c] + bias) as `s3r_conv_forward` runs a Conv(C -> 1, k = 1) layer ALONE: x
+    (B,C,n,n) or (B,C,n,n,n) with one edge n, weight any shape of C elements (an nn.Conv's (1,C,1,1,1)), bias one element or None;
+    act "none", "relu" or "sigmoid".  Returns (B,n,n[,n]).  Records no graph (`differentiable_head` does)."""
+    x, w, _ = _check_head(x, weight, act, "head")
+    b = _check_head_bias(bias, x.device, "head")
+    nd = x.dim() - 2
+    n = x.shape[2]
+    if nd not in (2, 3) or any(e != n for e in x.shape[2:]):
+        raise RuntimeError(f"head expects x (B,C,n,n) or (B,C,n,n,n) with one edge n, got {tuple(x.shape)}")
+    B, cin = x.shape[0], x.shape[1]
+    y = torch.empty((B,) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
+    if B == 0:
+        return y
+    lib = _lib.load()
+    desc = _lib.ConvDesc(_lib.OP_CONV, nd, B, cin, 1, n, 1, 1, 0, _lib.ACT[act], 0, -1, 0, 0, 0, 0, 0, 0, 0, 1, 0, 0.0)
+    stream = _stream_ptr(x.device)
+    elems = C.c_int64(0)
+    _lib.check(lib.s3r_conv_packed_elems(C.byref(desc), C.byref(elems)), "head: packed_elems")
+    pw = torch.empty(elems.value, dtype=torch.float32, device=x.device)
+    _lib.check(lib.s3r_conv_pack_weights(C.byref(desc), w.data_ptr(), pw.data_ptr(), stream), "head: pack_weights")
+    need = _lib.check(lib.s3r_conv_scratch_elems(C.byref(desc)), "head: scratch query")
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+    _lib.check(lib.s3r_conv_forward(C.byref(desc), x.data_ptr(), pw.data_ptr(), None, None if b is None else b.data_ptr(), y.data_ptr(),
+                                    scratch.data_ptr(), scratch.numel(), stream), "head")
+    return y
+
+
+@torch.no_grad()
+def head_backward(x: torch.Tensor, weight: torch.Tensor, y: Optional[torch.Tensor], grad_y: torch.Tensor, act: str,
+                  need_x: bool = True, need_w: bool = True, need_b: bool = True, scale: Optional[torch.Tensor] = None):
+    """(grad_x (the shape of x), grad_w (C), grad_bias (1)) of y = act((sum_c x[:, c] weight[c]) * scale + bias) for the output
+    gradient grad_y (B, ...), `None` for the sides not asked for (`s3r_head_backward`).  x (B,C,...) with any positions per sample, y
+    the layer's output (it may be None when act is "none"), scale one frozen fp32 element or None for 1.  One streaming pass, fixed
+    summation orders, no atomics: the same bits on every run.  Without need_x grad_x is not written, without need_w x is not read."""
+    x, w, S = _check_head(x, weight, act, "head_backward")
+    if not (need_x or need_w or need_b):
+        raise RuntimeError("head_backward needs need_x, need_w or need_b")
+    B, cin, dev = x.shape[0], x.shape[1], x.device
+
+    def flat(t, name):
+        t = _check_input(t, name, t.shape[1:])
+        if t.shape[0] != B or t.numel() != B * S:
+            raise RuntimeError(f"{name} must hold (B, positions) = ({B}, {S}) elements, got {tuple(t.shape)}")
+        return t
+
+    gy = flat(grad_y, "grad_y")
+    yy = None
+    if act != "none":
+        if y is None:
+            raise RuntimeError(f"head_backward: act {act!r} needs the layer's output y")
+        yy = flat(y, "y")
+    sc = _check_head_bias(scale, dev, "head_backward (scale)")
+    gx = torch.empty(x.shape, dtype=torch.float32, device=dev) if need_x else None
+    gw = torch.empty((cin,), dtype=torch.float32, device=dev) if need_w else None
+    gb = torch.empty((1,), dtype=torch.float32, device=dev) if need_b else None
+    if B == 0:                                     # an empty sum
+        for t in (gw, gb):
+            if t is not None:
+                t.zero_()
+        return gx, gw, gb
+    lib = _lib.load()
+    need = _lib.check(lib.s3r_head_backward_scratch_elems(B, cin, S), "head backward scratch query")
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    ptr = [None if t is None else t.data_ptr() for t in (sc, yy, gy, gx, gw, gb)]
+    _lib.check(lib.s3r_head_backward(x.data_ptr(), w.data_ptr(), *ptr, B, cin, S, _lib.ACT[act], scratch.data_ptr(), scratch.numel(),
+                                     _stream_ptr(dev)), "head backward")
+    return gx, gw, gb
+
+
+class _HeadFunction(torch.autograd.Function):
+    """`head` with `head_backward` as its derivative; saves x, weight and y"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act):
+        y = head(x, weight, bias, act)
+        ctx.act = act
+        ctx.save_for_backward(x, weight, y)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, weight, y = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        if not (need_x or need_w or need_b):
+            return None, None, None, None
+        gx, gw, gb = head_backward(x, weight, y, grad_y.contiguous().float(), ctx.act, need_x, need_w, need_b)
+        return gx, None if gw is None else gw.view(weight.shape), gb, None
+
+
+def differentiable_head(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], act: str = "sigmoid") -> torch.Tensor:
+    """`head` recorded for autograd: the same bits (the value of `s3r_conv_forward` on the head layer alone), with the deterministic
+    backward `head_backward`, called with exactly the sides autograd needs (`needs_input_grad`); gradients come back in the
+    parameters' own shapes.  A B = 0 input gives zero gradients without a kernel call."""
+    return _HeadFunction.apply(x, weight, bias, act)
 
 
 @torch.no_grad()
