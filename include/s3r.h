@@ -36,7 +36,8 @@
  * Conventions
  *   - every tensor is fp32, contiguous, NCHW / NCDHW, resident in device memory owned by the caller;
  *     the library never allocates, frees or synchronises;
- *   - `stream` is a hipStream_t (NULL = the default stream); work is enqueued, not waited for;
+ *   - `stream` is a hipStream_t (NULL = the default stream); work is enqueued, not waited for;  every entry point can be
+ *     stream-captured into a HIP graph and replayed on new data in the same buffers; the event profiler must be off while capturing;
  *   - return value: S3R_OK (0) or a negative s3r_status; s3r_last_error() gives a message for the
  *     calling thread; nothing throws across the ABI;
  *   - every tensor of one call must be < 2^31 elements and < 4 GiB (32-bit buffer offsets);

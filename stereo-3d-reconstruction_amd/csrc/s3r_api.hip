@@ -658,8 +658,8 @@ int chain_forward_impl(const s3r_layer* layers, int n_layers, const void* x, con
                     (long long)ws_elems);
     hipStream_t s = (hipStream_t)stream;
     if (ws_fresh && pl.total > 0) {   // zero halos (and everything else) once; later calls write interiors only
-        hipError_t e = hipMemsetAsync(ws, 0, (size_t)pl.total * sizeof(float), s);
-        if (e != hipSuccess) return hip_fail(e, "workspace memset");
+        hipError_t e = s3r::launch_zero_fill(ws, (long long)pl.total, s);
+        if (e != hipSuccess) return hip_fail(e, "workspace zero fill");
     }
     const void* cur = x;
     if ((x2 || x_u8) && (pl.pad_input || pl.r[0] != R_STEM))

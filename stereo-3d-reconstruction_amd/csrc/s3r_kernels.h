@@ -253,6 +253,7 @@ hipError_t launch_cost_volume(const float* fl, const float* fr, float* vol, int 
 hipError_t launch_cost_volume_wino(const float* fl, const float* fr, float* V, int B, int C, int D, int H, int W, int R, hipStream_t s);
 // parameter-general layers (s3r_general.hip): staged input (channel padding, padding halo, zero-stuffing), general weight packing,
 // LeakyReLU / ELU / Tanh as a pass of their own
+hipError_t launch_zero_fill(float* y, long long n, hipStream_t s);     // +0.0 into y[0 .. n), as a kernel (never a memset node)
 hipError_t launch_stage(const float* x, float* y, int B, int Cin, int CinPad, int nd, int n, int in_halo, int sp, int pe, int step,
                         hipStream_t s);
 hipError_t launch_pack_general(const float* w, float* wp, int Cin, int CinPad, int Cout, int CoutPad, int T, int flip, hipStream_t s);

@@ -834,7 +834,7 @@ int resolve_launch(const s3r_conv_desc* d, s3r::ConvParams* p, Launch* L) {
 // ---------------------------------------------------------------- chain planning
 // A chain gives every intermediate activation its own region of the caller's workspace, with the zero
 // halo the NEXT layer's gather wants; regions are written interior-only, so the halos stay zero from
-// the one memset that initialises the workspace (ws_fresh).
+// the one zero fill that initialises the workspace (ws_fresh: s3r::launch_zero_fill, a kernel).
 
 int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
