@@ -26,6 +26,8 @@
  *                                           order                                       (README.md:77)
  *   s3r_head_backward                       torch autograd's backward of the occupancy head's conv3d(64 -> 1, k = 1) + bias + sigmoid:
  *                                           one pass over the grid, fixed summation orders, no atomics   (README.md:77)
+ *   s3r_conv_backward (+ s3r_conv_adjoint_desc) torch autograd's backward of a conv3d / ConvTranspose3d + BN + activation block of the voxel
+ *                                           decoder: what `python3 runner.py` runs behind the loss for the up-path (README.md:77)
  *   s3r_disparity_wta, s3r_disparity_epe    predicted left / right disparity and its end-point error
  *                                           against the disp_%02d_{l,r}.exr ground truth (README.md:75-76)
  *   s3r_disparity_soft                      the same prediction as a sub-pixel soft-argmin, upsampled to the
@@ -70,7 +72,8 @@ extern "C" {
  * 16 up: other bits than ABI 7 for such a layer); s3r_profile_detail and record family 10 (aux passes).
  * s3r_disparity_soft and s3r_disparity_metrics were added later as new entry points only (no struct or existing signature changed):
  * the version stays 8.  s3r_chamfer_backward and s3r_linear_backward (+ its scratch query) likewise; s3r_voxel_bce_forward,
- * s3r_voxel_bce_backward and s3r_head_backward (+ its scratch query) likewise. */
+ * s3r_voxel_bce_backward and s3r_head_backward (+ its scratch query) likewise; s3r_conv_adjoint_desc and s3r_conv_backward (+ its scratch
+ * query) likewise: new entry points only, the version stays 8. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -453,6 +456,62 @@ int64_t s3r_head_backward_scratch_elems(int batch, int channels, int64_t voxels)
 int s3r_head_backward(const float* x, const float* w, const float* scale, const float* y, const float* grad_y, float* grad_x,
                       float* grad_w, float* grad_shift, int batch, int channels, int64_t voxels, int act, float* scratch,
                       int64_t scratch_elems, void* stream);
+
+/* Backward of ONE fp32 convolution layer  y = act(conv(x, w) * scale[o] + shift[o])  — S3R_OP_CONV or S3R_OP_DECONV, 2D or 3D, any k,
+ * stride, pad and output padding.  x (B,cin,n..); y, grad_y, gs (B,cout,m..); scale (cout) or NULL for 1 (frozen: it gets no gradient, as in
+ * s3r_head_backward); grad_w in the layer's torch weight shape (Conv: [cout][cin][k..]; ConvTranspose: [cin][cout][k..]); grad_shift (cout).
+ * The three entry points take fp32 layers with dilation 1 on plain tensors only: S3R_BF16, S3R_OP_LINEAR, dilation > 1, a layout other
+ * than S3R_LAYOUT_PLAIN, a halo, or an activation other than none / ReLU / sigmoid is S3R_ERR_INVALID before anything is enqueued.
+ *
+ * The input gradient needs no kernel of its own: it is the FORWARD of the adjoint layer on gs, with the layer's own weight tensor read in
+ * torch's layout for the other operator — no flip, no re-layout:
+ *   Conv(cin -> cout, k, s, p) over edge n:          grad_x = ConvTranspose(cout -> cin, k, s, p, out_pad = (n + 2 p - k) mod s)(gs), the
+ *                                                    weight [cout][cin][k..] read as a ConvTranspose weight [cin' = cout][cout' = cin][k..];
+ *   ConvTranspose(cin -> cout, k, s, p, out_pad):    grad_x = Conv(cout -> cin, k, s, p)(gs), the weight [cin][cout][k..] read as a Conv
+ *                                                    weight [cout' = cin][cin' = cout][k..].
+ * s3r_conv_adjoint_desc (host only) fills that layer's descriptor: op swapped, cin / cout swapped, in_size = d's output edge, k / stride /
+ * pad copied, out_pad by the rule above, act none, halos 0, layouts PLAIN, algo AUTO, dilation 1; batch, ndim and tag copied.  A caller
+ * packs the layer's own torch-layout weight with s3r_conv_pack_weights(adj, w, ...) and runs adj as a forward on gs with scale and shift
+ * NULL: s3r_conv_forward(adj, gs, packed, NULL, NULL, grad_x, ...) where adj's kernel takes an unpadded input (s3r_conv_forward says so),
+ * else as a one-layer s3r_chain_forward, which pads an unpadded input itself.  grad_x then has the forward kernels' accuracy and their
+ * batch-independent bits.
+ *
+ * s3r_conv_backward computes, in this order of dependence:
+ *   g   the pre-activation gradient, s3r_linear_backward's rule, fp32, nothing fused:  none: g = grad_y;  ReLU: g = (y > 0.f) ? grad_y : 0.f
+ *       (a NaN y gives 0);  sigmoid: t = 1 - y; u = y * t; g = grad_y * u — every operation rounded once, in this order;
+ *   gs[b][o][.] = g * scale[o], rounded once; g itself when scale is NULL.  Bit for bit.  gs is an OUTPUT (the caller hands it to grad_x's
+ *       forward call), not scratch;
+ *   grad_shift[o] = sum_{b, pos} g[b][o][pos], bit for bit, in the head backward's order (s3r_head_backward above) with channel o's S = m^ndim
+ *       positions of a sample in place of the sample's: chunks of 512 consecutive positions, lane L owns the 8 positions 256 j + 4 L + i
+ *       and adds them in ascending position to a partial that starts as +0.0, the halving tree over the 64 partials, the chunk sums in
+ *       ascending chunk order per sample starting from chunk 0's, the per-sample partials in ascending b starting from sample 0's;
+ *   grad_w[a][f][t] = sum_{b, q over the coarse grid} A[b][a][q] * F[b][f][q * s - p + t]  (per axis; F reads 0 outside its grid), where the
+ *       coarse grid is the Conv's output or the ConvTranspose's input — Conv: A = gs, F = x; ConvTranspose: A = x, F = gs — on
+ *       v_mfma_f32_32x32x2_f32.  The sum over (b, q) is cut into slices that are a function of the layer's PER-SAMPLE geometry only — never
+ *       of B, the device or an address; a slice never spans two samples, and inside one q ascends.  The slices are written as slabs into
+ *       `scratch`, and a finish kernel adds them in ascending (sample, slice) order: per element, a sample's slabs in ascending slice order
+ *       starting from its slab 0, then the per-sample partials in ascending b starting from sample 0's.  So: no atomics; the same bits on
+ *       every run, at every 4-byte-aligned address and with any scratch contents on entry; a sample's partial is the same in every batch it
+ *       appears in (grad_w of a batch equals, bit for bit, the ascending fp32 sum of the B = 1 results of its samples).
+ *       Coarse positions, channels and taps beyond the tensors are loaded from clamped addresses and replaced by 0 in BOTH operands (0 * NaN
+ *       would be NaN); they add +0.0 to accumulators that started as +0.0, which changes no bit.
+ * gs, grad_w and grad_shift may each be NULL: that output is not computed, and the computed ones keep the bits of the full call; all three
+ * NULL is S3R_ERR_INVALID.  grad_w needs gs: with gs NULL it lives in scratch.  y may be NULL when act is none (y NULL with ReLU or sigmoid:
+ * S3R_ERR_INVALID), x when grad_w is.  Outputs are overwritten, never accumulated into.  batch >= 0 (0 launches nothing and returns
+ * S3R_OK; the query returns 0); every tensor < 2^31 elements and < 4 GiB.
+ * `scratch`: s3r_conv_backward_scratch_elems floats (gs, the chunk sums, the slabs), sized for the worst case over the outputs asked for,
+ * independent of the device, monotone in batch; a shorter (or NULL) one is S3R_ERR_WORKSPACE.  Nothing is enqueued when the call is refused.
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new data in the same buffers).
+ * Profiler: ONE record of family 0 whose tag is S3R_CONV_BACKWARD_TAG + d->tag (a layer's forward record keeps d->tag; under
+ * s3r_profile_detail(1) the prep pass and the two finish passes get family-10 records of the same tag nested inside it); `flops` =
+ * 2 B Q Ca Cf k^ndim when grad_w is computed (Q coarse positions per sample), else 0; `bytes` = the tensors the call must read and write
+ * (grad_y; y unless act is none; scale when given; gs when given; x and grad_w; grad_shift). */
+#define S3R_CONV_BACKWARD_TAG 1000000
+int s3r_conv_adjoint_desc(const s3r_conv_desc* d, s3r_conv_desc* adj);
+int64_t s3r_conv_backward_scratch_elems(const s3r_conv_desc* d);
+int s3r_conv_backward(const s3r_conv_desc* d, const float* x, const float* y, const float* grad_y, const float* scale, float* gs,
+                      float* grad_w, float* grad_shift, float* scratch, int64_t scratch_elems, void* hip_stream);
 
 /* Disparity read-out: winner-take-all over the shift-and-diff costs of the cost volume (same features, same
  * |L - R shifted| costs, volume never materialised).  feat_* (B,C,H,W) fp32; disp_* (B,H,W) fp32, integer-valued,

@@ -19,6 +19,7 @@ ACT = {"none": 0, "relu": 1, "sigmoid": 2, "leaky_relu": 3, "elu": 4, "tanh": 5}
 FAMILY = {0: "conv_mfma", 1: "stem", 2: "head", 3: "cost_volume", 4: "linear", 5: "chamfer", 6: "iou", 7: "pack",
           8: "pad_copy", 9: "disparity", 10: "aux"}      # aux: transform / finish passes, nested inside their layer's conv_mfma record
 ABI_VERSION = 8
+CONV_BACKWARD_TAG = 1000000      # S3R_CONV_BACKWARD_TAG: a conv backward's profiler record carries this + the layer's tag
 ALGO_AUTO, ALGO_DIRECT, ALGO_WINOGRAD = 0, 1, 2
 ALGO = {None: 0, "auto": 0, "direct": 1, "winograd": 2, False: 1, True: 2}
 RAN = {0: "direct", 1: "winograd-serial", 2: "winograd-class-parallel", 3: "winograd-dual", 4: "winograd-2axis", 5: "winograd-3axis", 6: "winograd-3axis-class-parallel"}
@@ -94,6 +95,10 @@ SIGNATURES = {
     "s3r_head_backward_scratch_elems": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
     "s3r_head_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "s3r_conv_adjoint_desc": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
+    "s3r_conv_backward_scratch_elems": (C.c_int64, [C.POINTER(ConvDesc)]),
+    "s3r_conv_backward": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int64, C.c_void_p]),
     "s3r_disparity_wta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_void_p]),
     "s3r_disparity_epe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),

@@ -1039,6 +1039,88 @@ int s3r_head_backward(const float* x, const float* w, const float* scale, const 
     return S3R_OK;
 }
 
+// what the conv-backward entry points take: an fp32 Conv / ConvTranspose, dilation 1, plain tensors without halos, none / relu / sigmoid.
+// `batch_min` 0: s3r_conv_backward and its scratch query accept an empty batch.  Fills the geometry (of batch max(batch, 1)) and tiling
+static int convbwd_check(const s3r_conv_desc* d, const char* who, int batch_min, Geo* g, s3r::ConvBwdGeo* cg) {
+    if (!d) return fail(S3R_ERR_INVALID, "%s: null descriptor", who);
+    if (d->dtype != S3R_F32) return fail(S3R_ERR_INVALID, "%s: fp32 layers only (dtype %d)", who, d->dtype);
+    if (d->op != S3R_OP_CONV && d->op != S3R_OP_DECONV)
+        return fail(S3R_ERR_INVALID, "%s: Conv / ConvTranspose layers only (op %d; linear layers have s3r_linear_backward)", who, d->op);
+    if (dil_of(d) != 1) return fail(S3R_ERR_INVALID, "%s: dilation 1 only (got %d)", who, d->dilation);
+    if (d->in_layout != S3R_LAYOUT_PLAIN || d->out_layout != S3R_LAYOUT_PLAIN || d->in_halo != 0 || d->out_halo != 0)
+        return fail(S3R_ERR_INVALID, "%s: plain tensors only (layouts PLAIN, halos 0)", who);
+    if (d->act < S3R_ACT_NONE || d->act > S3R_ACT_SIGMOID) return fail(S3R_ERR_INVALID, "%s takes none / relu / sigmoid (act %d)", who, d->act);
+    if (d->batch < batch_min) return fail(S3R_ERR_INVALID, "%s: batch must be >= %d (got %d)", who, batch_min, d->batch);
+    s3r_conv_desc one = *d;
+    if (one.batch == 0) one.batch = 1;
+    int rc = geometry(&one, g);
+    if (rc) return rc;
+    if (g->w_elems >= kMaxElems) return fail(S3R_ERR_INVALID, "%s: weight of 2^31 elements or more", who);
+    if (!s3r::convbwd_geo(d->op == S3R_OP_DECONV, d->ndim, d->cin, d->cout, g->in, g->out, d->k, d->stride, d->pad, cg))
+        return fail(S3R_ERR_INVALID, "%s: no tiling of the weight-gradient GEMM fits this kernel size / stride (k %d, stride %d)", who, d->k,
+                    d->stride);
+    if ((int64_t)d->batch * cg->nsl * cg->tiles >= kMaxElems) return fail(S3R_ERR_INVALID, "%s: too many workgroups: split the batch", who);
+    return S3R_OK;
+}
+
+int s3r_conv_adjoint_desc(const s3r_conv_desc* d, s3r_conv_desc* adj) {
+    Geo g, ga;
+    s3r::ConvBwdGeo cg;
+    if (!adj) return fail(S3R_ERR_INVALID, "s3r_conv_adjoint_desc: null output descriptor");
+    int rc = convbwd_check(d, "s3r_conv_adjoint_desc", 1, &g, &cg);
+    if (rc) return rc;
+    s3r_conv_desc a;
+    memset(&a, 0, sizeof(a));
+    a.op = d->op == S3R_OP_CONV ? S3R_OP_DECONV : S3R_OP_CONV;
+    a.ndim = d->ndim; a.batch = d->batch; a.tag = d->tag;
+    a.cin = d->cout; a.cout = d->cin;
+    a.in_size = g.out;
+    a.k = d->k; a.stride = d->stride; a.pad = d->pad;
+    a.act = S3R_ACT_NONE; a.tile = -1; a.dtype = S3R_F32; a.algo = S3R_ALGO_AUTO; a.dilation = 1;
+    a.out_pad = d->op == S3R_OP_CONV ? (d->in_size + 2 * d->pad - d->k) % d->stride : 0;
+    rc = geometry(&a, &ga);                                              // (a Conv with pad > k - 1 has no ConvTranspose this library runs)
+    if (rc) return rc;
+    if (ga.out != d->in_size) return fail(S3R_ERR_INVALID, "s3r_conv_adjoint_desc: internal: adjoint output edge %d != input edge %d", ga.out, d->in_size);
+    *adj = a;
+    return S3R_OK;
+}
+
+int64_t s3r_conv_backward_scratch_elems(const s3r_conv_desc* d) {
+    Geo g;
+    s3r::ConvBwdGeo cg;
+    int rc = convbwd_check(d, "s3r_conv_backward_scratch_elems", 0, &g, &cg);
+    if (rc) return rc;
+    if (d->batch == 0) return 0;
+    return s3r::conv_backward_scratch_elems(cg, d->batch, d->cout, g.out_sp);
+}
+
+int s3r_conv_backward(const s3r_conv_desc* d, const float* x, const float* y, const float* grad_y, const float* scale, float* gs,
+                      float* grad_w, float* grad_shift, float* scratch, int64_t scratch_elems, void* hip_stream) {
+    if (!gs && !grad_w && !grad_shift)
+        return fail(S3R_ERR_INVALID, "conv backward: gs, grad_w and grad_shift are all NULL (each may be: it is not computed)");
+    Geo g;
+    s3r::ConvBwdGeo cg;
+    int rc = convbwd_check(d, "s3r_conv_backward", 0, &g, &cg);
+    if (rc) return rc;
+    if (d->batch == 0) return S3R_OK;
+    if (!grad_y || (grad_w && !x)) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    if (d->act != S3R_ACT_NONE && !y) return fail(S3R_ERR_INVALID, "conv backward: y is NULL (it may be only when act is none)");
+    const int64_t need = s3r::conv_backward_scratch_elems(cg, d->batch, d->cout, g.out_sp);
+    if (!scratch || scratch_elems < need)
+        return fail(S3R_ERR_WORKSPACE, "conv backward needs %lld floats of scratch (s3r_conv_backward_scratch_elems), got %lld",
+                    (long long)need, (long long)(scratch ? scratch_elems : 0));
+    hipStream_t s = (hipStream_t)hip_stream;
+    const double B = d->batch, Y = B * d->cout * (double)g.out_sp, X = B * d->cin * (double)g.in_sp;
+    const double flops = grad_w ? 2.0 * B * (double)cg.Q * cg.Ca * cg.Cf * cg.T : 0.0;
+    const double elems = Y * (d->act != S3R_ACT_NONE ? 2.0 : 1.0) + (scale ? d->cout : 0.0) + (gs ? Y : 0.0) +
+                         (grad_w ? X + (double)g.w_elems : 0.0) + (grad_shift ? d->cout : 0.0);
+    ProfScope ps(s, F_MFMA, S3R_CONV_BACKWARD_TAG + d->tag, flops, 4.0 * elems);
+    hipError_t e = s3r::launch_conv_backward(cg, d->op == S3R_OP_DECONV, x, y, grad_y, scale, gs, grad_w, grad_shift, d->batch, d->cout,
+                                             g.out_sp, d->act, scratch, s, &ps.launches);
+    if (e != hipSuccess) return hip_fail(e, "conv backward launch");
+    return S3R_OK;
+}
+
 int s3r_disparity_wta(const float* feat_l, const float* feat_r, float* disp_l, float* disp_r, int batch, int channels,
                       int height, int width, int max_disp, void* stream) {
     if (!feat_l || !feat_r || !disp_l || !disp_r) return fail(S3R_ERR_INVALID, "null tensor pointer");

@@ -292,6 +292,29 @@ hipError_t launch_head_backward(const float* x, const float* w, const float* sca
                                 float* gw, float* gshift, int B, int C, int64_t S, int act, float* scratch, hipStream_t s,
                                 int* launches);
 int64_t head_backward_scratch_elems(int B, int C, int64_t S);
+// s3r_conv_bwd.hip: backward of one fp32 Conv / ConvTranspose layer except its input gradient (that is the adjoint layer's forward):
+// gs = g * scale, grad_shift in the head backward's order, grad_w as a sliced GEMM whose slabs are added in a fixed order.
+// ConvBwdGeo: the weight-gradient GEMM's tiling, a function of the layer's per-sample geometry only (convbwd_geo; false: no tiling fits)
+struct ConvBwdGeo {
+    int nd, k, s, p;
+    int Ca, Cf;                  // channels on the coarse / fine grid
+    int mc, nf;                  // coarse / fine edge
+    long long Q, Pf;             // positions per channel on the coarse / fine grid
+    int T, To;                   // taps k^nd, outer taps k^(nd - 1)
+    int NT, ntg;                 // taps along W per wave, groups of them
+    int nrows;                   // coarse rows (lines along W) per sample
+    int WL, WLP, R, nseg;        // a chunk: R rows x WL positions (WLP: rounded up to even), nseg segments per row
+    int FL, astr, fstr;          // staged fine columns per row; LDS row strides (odd)
+    int lds_bytes;
+    int nchunks, cps, nsl;       // chunks per sample, chunks per slice, slices per sample
+    int nag, nft, tiles;         // 128-row groups, 32-channel tiles, workgroups per slice
+    long long slab;              // Ca Cf T
+};
+bool convbwd_geo(int deconv, int nd, int cin, int cout, int in_size, int out_size, int k, int s, int p, ConvBwdGeo* g);
+int64_t conv_backward_scratch_elems(const ConvBwdGeo& g, int B, int cout, int64_t S);
+hipError_t launch_conv_backward(const ConvBwdGeo& g, int deconv, const float* x, const float* y, const float* gy, const float* scale,
+                                float* gs, float* gw, float* gshift, int B, int cout, int64_t S, int act, float* scratch, hipStream_t s,
+                                int* launches);
 // s3r_voxel_loss.hip: BCELoss's per-element rule with a per-sample sum in a fixed order (loss_sum or loss_elem may be NULL), and its
 // elementwise gradient
 hipError_t launch_voxel_bce(const float* pred, const float* target, float* loss_sum, float* loss_elem, int B, int64_t V,

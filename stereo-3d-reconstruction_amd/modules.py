@@ -6,12 +6,15 @@ PyTorch model — but whose `forward` enqueues the hand-written HIP kernels of l
 its C-ABI.  PyTorch is plumbing here (device memory, streams); no torch conv / BN op runs in any
 forward below, and nothing falls back to the CPU: without the HIP library every forward raises.
 
-Forward-only (inference, eval-mode BatchNorm): outputs carry no autograd graph.
+Inference modules (eval-mode BatchNorm): their forwards carry no autograd graph; the `differentiable_*` functions and methods below
+record one, with the library's own deterministic backward kernels behind it.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
+import weakref
 from typing import Dict, List, Optional, Sequence
 
 import torch
@@ -669,6 +672,42 @@ class Decoder(_HipChain):
         blk: _Block = getattr(self, l.name)
         return differentiable_head(x, blk.conv.weight, blk.conv.bias, l.act)
 
+    def differentiable_features(self, x: torch.Tensor, start: str = "d3") -> torch.Tensor:
+        """Layers `start` .. d3 recorded for autograd on this module's OWN parameters: x is `start`'s input (for "d3" the
+        (B,128,16,16,16) activation `Stereo2Voxel.trunk_features(l, r, upto="d2")` returns), the result d3's (B,64,32,32,32) output —
+        what `features()` returns, with a graph.  Every layer runs as `differentiable_conv`: its kernel's forward under the AUTO
+        algorithm, `s3r_conv_backward` and the adjoint layer's forward behind it.  A block's BatchNorm stays in eval mode and folded:
+        `scale` is `_Block.folded()`'s scale (detached: `bn.weight` is FROZEN on this path, its gradient stays None, and so are the
+        running statistics); `shift` is folded()'s expression, bn.bias + (conv.bias - running_mean) * scale, evaluated with torch
+        operations under grad, so grad_shift reaches `bn.bias` and `conv.bias` through torch.
+        With start = "d3" the value HAS the bits of `features()` (the chain up to d3): measured bit-identical at B = 1, 2 and 5 on an
+        MI355X (LAB_NOTES, "Conv backward") and pinned by
+        tests/test_conv_backward_gpu.py::test_standalone_d3_forward_has_the_bits_of_the_chain on THIS method's output — both run d3's
+        three-axis Winograd form on the same input, and its launch forms agree bit for bit."""
+        self._fp32_only("Decoder.differentiable_features")
+        if start not in self.names[:-1]:
+            raise RuntimeError(f"start must be one of {self.names[:-1]}, got {start!r}")
+        first = self.names.index(start)
+        n_in = self._sizes()[first][0]
+        x = _check_input(x, "x", (self._layers[first].cin,) + (n_in,) * 3)
+        for l in self._layers[first:-1]:
+            blk: _Block = getattr(self, l.name)
+            scale, _ = blk.folded()
+            if scale is None:
+                shift = blk.conv.bias
+            else:
+                shift = blk.bn.bias + (blk.conv.bias - blk.bn.running_mean.detach()) * scale
+            x = differentiable_conv(x, blk.conv.weight, scale, shift, l)
+        return x
+
+    def differentiable_tail(self, x: torch.Tensor, start: str = "d3") -> torch.Tensor:
+        """`differentiable_head(differentiable_features(x, start))`: layers `start` .. d4 under autograd, (B,32,32,32) occupancy out.
+        d4's standalone kernel agrees with the fused d3 + d4 pass of `forward` to fp32 rounding (`differentiable_head`).  `bn.weight`
+        is frozen (see `differentiable_features`).  The fine-tune step on a frozen trunk:
+        `VoxelBCELoss()(model.decoder.differentiable_tail(model.trunk_features(l, r, upto="d2")), gt).backward()`."""
+        self._fp32_only("Decoder.differentiable_tail")
+        return self.differentiable_head(self.differentiable_features(x, start))
+
 
 class VolumeEncoder(_HipChain):
     """The down half of the hourglass alone (Stereo2Point): cost volume -> (B,512,4,4,4) latent."""
@@ -830,13 +869,24 @@ class Stereo2Voxel(_DisparityMixin, nn.Module):
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
     @torch.no_grad()
+    def trunk_features(self, left: torch.Tensor, right: torch.Tensor, upto: str = "d2") -> torch.Tensor:
+        """The frozen trunk — encoder, cost volume, decoder up to the layer `upto` (any decoder layer in front of d4) — without a graph:
+        the fp32 activation the layer behind `upto` reads.  `decoder.differentiable_tail(model.trunk_features(l, r, upto="d2"))` is
+        the trainable part d3 + d4:
+        `VoxelBCELoss()(model.decoder.differentiable_tail(model.trunk_features(l, r, upto="d2")), gt).backward()`.  fp32 models only."""
+        self.decoder._fp32_only("Stereo2Voxel.trunk_features")
+        if upto not in self.decoder.names[:-1]:
+            raise RuntimeError(f"upto must be one of {self.decoder.names[:-1]}, got {upto!r}")
+        outs = list(self._decoded(left, right, upto=upto))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    @torch.no_grad()
     def head_features(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
         """The frozen trunk alone — encoder, cost volume, decoder up to d3 — without a graph: the fp32 (B,64,32,32,32) activation the
-        occupancy head reads (the counterpart of `Stereo2Point.latent`).  `decoder.differentiable_head(model.head_features(l, r))`
-        is the trainable part.  fp32 models only."""
+        occupancy head reads (the counterpart of `Stereo2Point.latent`): `trunk_features(upto="d3")`.
+        `decoder.differentiable_head(model.head_features(l, r))` is the trainable part.  fp32 models only."""
         self.decoder._fp32_only("Stereo2Voxel.head_features")
-        outs = list(self._decoded(left, right, upto=Decoder.FEATURES))
-        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+        return self.trunk_features(left, right, upto=Decoder.FEATURES)
 
     @torch.no_grad()
     def autotune(self, left: torch.Tensor, right: torch.Tensor, rounds: int = 3, log=None):
@@ -1318,6 +1368,179 @@ def differentiable_head(x: torch.Tensor, weight: torch.Tensor, bias: Optional[to
     backward `head_backward`, called with exactly the sides autograd needs (`needs_input_grad`); gradients come back in the
     parameters' own shapes.  A B = 0 input gives zero gradients without a kernel call."""
     return _HeadFunction.apply(x, weight, bias, act)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# One convolution layer under autograd: the forward as a one-layer chain, the backward as s3r_conv_backward + the adjoint layer's forward
+_CONV_OPS = ("conv2d", "conv3d", "deconv2d", "deconv3d")
+_PACKED_FOR = collections.OrderedDict()      # (id(weight), device, descriptor) -> (weakref to the weight, version, packed image)
+_PACKED_MAX = 32
+
+
+def _packed_for(weight: torch.Tensor, desc) -> torch.Tensor:
+    """`weight` (torch layout) packed for `desc`: ONE image per (weight object, layer), valid for the `_version` it was packed at — what
+    `_HipChain._ensure_packed` keys on too.  An in-place update of the parameter (an optimizer step) bumps `_version`, and the new image
+    REPLACES the old one.  The weak reference tells a live tensor from another one that got a dead one's `id` (an address is no
+    identity either: the allocator hands a freed block to the next tensor of the same size)."""
+    sig = tuple(getattr(desc, n) for n in ("op", "ndim", "cin", "cout", "in_size", "k", "stride", "pad", "out_pad", "dtype", "algo"))
+    key = (id(weight), str(weight.device), sig)
+    hit = _PACKED_FOR.get(key)
+    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
+        _PACKED_FOR.move_to_end(key)
+        return hit[2]
+    lib = _lib.load()
+    one = _lib.ConvDesc.from_buffer_copy(desc)
+    one.batch = 1
+    n = C.c_int64(0)
+    _lib.check(lib.s3r_conv_packed_elems(C.byref(one), C.byref(n)), "packed_elems")
+    w = weight.detach().float().contiguous()
+    pw = torch.empty(n.value, dtype=torch.float32, device=w.device)
+    _lib.check(lib.s3r_conv_pack_weights(C.byref(one), w.data_ptr(), pw.data_ptr(), _stream_ptr(w.device)), "pack_weights")
+    _PACKED_FOR[key] = (weakref.ref(weight), weight._version, pw)
+    _PACKED_FOR.move_to_end(key)
+    for k in [k for k, v in _PACKED_FOR.items() if v[0]() is None]:      # images of tensors that are gone
+        del _PACKED_FOR[k]
+    while len(_PACKED_FOR) > _PACKED_MAX:
+        _PACKED_FOR.popitem(last=False)
+    return pw
+
+
+def _run_one_layer(desc, x: torch.Tensor, pw: torch.Tensor, scale, shift, y: torch.Tensor) -> torch.Tensor:
+    """One layer through `s3r_chain_forward`: `s3r_conv_forward` behind the halo-padded copy of an unpadded input that the layer's
+    kernel may read its zero padding from (the chain plans that copy itself; a single `s3r_conv_forward` call refuses such a layer)."""
+    lib = _lib.load()
+    arr = (_lib.Layer * 1)()
+    arr[0].desc = desc
+    arr[0].packed_w = pw.data_ptr()
+    arr[0].scale = scale.data_ptr() if scale is not None else None
+    arr[0].shift = shift.data_ptr() if shift is not None else None
+    need = _lib.check(lib.s3r_chain_workspace_elems(arr, 1), "workspace query")
+    ws = torch.empty(max(need, 1), dtype=torch.float32, device=x.device)
+    _lib.check(lib.s3r_chain_forward(arr, 1, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), 1, _stream_ptr(x.device)),
+               "one-layer chain")
+    return y
+
+
+def _check_conv(x, weight, layer, who):
+    if layer.op not in _CONV_OPS:
+        raise RuntimeError(f"{who} takes a conv2d / conv3d / deconv2d / deconv3d layer, got {layer.op!r}")
+    if layer.act not in _LINEAR_ACTS:
+        raise RuntimeError(f"{who}: act must be one of {_LINEAR_ACTS}, got {layer.act!r}")
+    if layer.dil != 1:
+        raise RuntimeError(f"{who}: dilation 1 only")
+    nd = spec.ndim(layer)
+    if not isinstance(x, torch.Tensor) or x.dim() != nd + 2 or x.shape[1] != layer.cin or any(e != x.shape[2] for e in x.shape[2:]):
+        raise RuntimeError(f"{who} expects x (B, {layer.cin}, n{', n' * (nd - 1)}) with one edge n, got {tuple(getattr(x, 'shape', ()))}")
+    x = _check_input(x.detach(), "x", x.shape[1:])
+    want = ((layer.cin, layer.cout) if layer.op.startswith("deconv") else (layer.cout, layer.cin)) + (layer.k,) * nd
+    w = weight.detach()
+    if tuple(w.shape) != want or w.device != x.device or w.dtype != torch.float32 or not w.is_contiguous():
+        raise RuntimeError(f"{who}: weight must be a contiguous fp32 tensor of shape {want} on {x.device}, got {tuple(w.shape)}")
+    n = x.shape[2]
+    m = spec.out_size(layer, n)
+    if m <= 0:
+        raise RuntimeError(f"{who}: the layer has no output over an edge of {n}")
+    return x, w, n, (x.shape[0], layer.cout) + (m,) * nd
+
+
+def _check_channel_vector(v, cout, device, who, name):
+    if v is None:
+        return None
+    v = v.detach()
+    if tuple(v.shape) != (cout,) or v.device != device or v.dtype != torch.float32:
+        raise RuntimeError(f"{who}: {name} must be a fp32 tensor of shape ({cout},) on {device}")
+    return v.contiguous()
+
+
+@torch.no_grad()
+def conv_forward(x: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
+                 layer: spec.Layer) -> torch.Tensor:
+    """act(conv(x, weight) * scale + shift) of ONE arch_spec layer (conv2d / conv3d / deconv2d / deconv3d, dilation 1, act none /
+    relu / sigmoid) under the library's AUTO algorithm, as a one-layer `s3r_chain_forward`.  Records no graph."""
+    x, w, n, yshape = _check_conv(x, weight, layer, "conv_forward")
+    sc = _check_channel_vector(scale, layer.cout, x.device, "conv_forward", "scale")
+    sh = _check_channel_vector(shift, layer.cout, x.device, "conv_forward", "shift")
+    y = torch.empty(yshape, dtype=torch.float32, device=x.device)
+    if x.shape[0] == 0:
+        return y
+    desc = _lib.make_desc(layer, x.shape[0], n)
+    return _run_one_layer(desc, x, _packed_for(weight, desc), sc, sh, y)
+
+
+@torch.no_grad()
+def conv_backward(x: torch.Tensor, weight: torch.Tensor, y: Optional[torch.Tensor], grad_y: torch.Tensor, layer: spec.Layer,
+                  scale: Optional[torch.Tensor] = None, need_x: bool = True, need_w: bool = True, need_shift: bool = True):
+    """(grad_x, grad_w, grad_shift) of y = act(conv(x, weight) * scale + shift) for the output gradient grad_y, `None` for the sides not
+    asked for.  ONE `s3r_conv_backward` call (gs = g * scale, grad_w in the weight's torch shape, grad_shift (cout): fixed summation
+    orders, no atomics, the same bits on every run and for every batch a sample appears in) and then, when need_x, the forward of the
+    adjoint layer (`s3r_conv_adjoint_desc`) on gs with this layer's own weight tensor, packed once per weight tensor and `_version`.  y may
+    be None when the layer's act is "none"; scale (cout) is frozen: it gets no gradient."""
+    x, w, n, yshape = _check_conv(x, weight, layer, "conv_backward")
+    if not (need_x or need_w or need_shift):
+        raise RuntimeError("conv_backward needs need_x, need_w or need_shift")
+    B, dev = x.shape[0], x.device
+    gy = _check_input(grad_y, "grad_y", yshape[1:])
+    if gy.shape[0] != B:
+        raise RuntimeError(f"grad_y must hold {B} samples, got {gy.shape[0]}")
+    yy = None
+    if layer.act != "none":
+        if y is None:
+            raise RuntimeError(f"conv_backward: act {layer.act!r} needs the layer's output y")
+        yy = _check_input(y.detach(), "y", yshape[1:])
+        if yy.shape[0] != B:
+            raise RuntimeError(f"y must hold {B} samples, got {yy.shape[0]}")
+    sc = _check_channel_vector(scale, layer.cout, dev, "conv_backward", "scale")
+    gx = torch.empty(x.shape, dtype=torch.float32, device=dev) if need_x else None
+    gs = torch.empty(yshape, dtype=torch.float32, device=dev) if need_x else None
+    gw = torch.empty(w.shape, dtype=torch.float32, device=dev) if need_w else None
+    gb = torch.empty((layer.cout,), dtype=torch.float32, device=dev) if need_shift else None
+    if B == 0:                                     # an empty sum
+        for t in (gw, gb):
+            if t is not None:
+                t.zero_()
+        return gx, gw, gb
+    lib = _lib.load()
+    desc = _lib.make_desc(layer, B, n)
+    need = _lib.check(lib.s3r_conv_backward_scratch_elems(C.byref(desc)), "conv backward scratch query")
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    ptr = [None if t is None else t.data_ptr() for t in (x if need_w else None, yy, gy, sc, gs, gw, gb)]
+    _lib.check(lib.s3r_conv_backward(C.byref(desc), *ptr, scratch.data_ptr(), scratch.numel(), _stream_ptr(dev)), "conv backward")
+    if need_x:
+        adj = _lib.ConvDesc()
+        _lib.check(lib.s3r_conv_adjoint_desc(C.byref(desc), C.byref(adj)), "conv adjoint descriptor")
+        _run_one_layer(adj, gs, _packed_for(weight, adj), None, None, gx)
+    return gx, gw, gb
+
+
+class _ConvFunction(torch.autograd.Function):
+    """`conv_forward` with `conv_backward` as its derivative; saves x, weight, scale and y"""
+
+    @staticmethod
+    def forward(ctx, x, weight, scale, shift, layer):
+        y = conv_forward(x, weight, scale, shift, layer)
+        ctx.layer = layer
+        ctx.has_scale = scale is not None
+        ctx.save_for_backward(x, weight, y, *((scale,) if scale is not None else ()))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        x, weight, y = ctx.saved_tensors[:3]
+        scale = ctx.saved_tensors[3] if ctx.has_scale else None
+        need_x, need_w, need_shift = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        if not (need_x or need_w or need_shift):
+            return None, None, None, None, None
+        gx, gw, gb = conv_backward(x, weight, y, grad_y.contiguous().float(), ctx.layer, scale, need_x, need_w, need_shift)
+        return gx, gw, None, gb, None
+
+
+def differentiable_conv(x: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
+                        layer: spec.Layer) -> torch.Tensor:
+    """`conv_forward` recorded for autograd: the value of the layer's kernel under the AUTO algorithm, with the deterministic backward
+    `conv_backward`, called with exactly the sides autograd needs (`needs_input_grad` of x, weight and shift).  `scale` is frozen: its
+    gradient is `None` (a folded BatchNorm scale: `bn.weight` is not trained through this path)."""
+    return _ConvFunction.apply(x, weight, scale, shift, layer)
 
 
 @torch.no_grad()
