@@ -11,6 +11,8 @@
  *                                           dataset transform's uint8 -> float32 / 255 as well (requirements.txt:5)
  *   s3r_cost_volume_forward                 the per-disparity shift/subtract Python loop that builds the
  *                                           disparity cost volume                       (README.md:75-76)
+ *   s3r_cost_volume_backward                torch autograd's backward of that loop (slice assignments of differences): what
+ *                                           `python3 runner.py` runs behind the loss between decoder and encoder (README.md:75-76)
  *   s3r_decoder_forward (+conv/deconv/head) the torch conv3d / ConvTranspose3d + BN + ReLU + sigmoid
  *                                           calls of the voxel decoder                  (README.md:77)
  *   s3r_linear_forward                      the point decoder's nn.Linear layers        (README.md:36)
@@ -73,7 +75,7 @@ extern "C" {
  * s3r_disparity_soft and s3r_disparity_metrics were added later as new entry points only (no struct or existing signature changed):
  * the version stays 8.  s3r_chamfer_backward and s3r_linear_backward (+ its scratch query) likewise; s3r_voxel_bce_forward,
  * s3r_voxel_bce_backward and s3r_head_backward (+ its scratch query) likewise; s3r_conv_adjoint_desc and s3r_conv_backward (+ its scratch
- * query) likewise: new entry points only, the version stays 8. */
+ * query) likewise; s3r_cost_volume_backward likewise: new entry points only, the version stays 8. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -311,6 +313,33 @@ int s3r_cost_volume_forward_wino2(const float* feat_left, const float* feat_righ
 /* the same on channels-last bf16 features (B,H,W,C) -> volume (B,D+2h,H+2h,W+2h,2C); channels % 8 == 0 */
 int s3r_cost_volume_forward_bf16(const void* feat_left, const void* feat_right, void* volume, int batch, int channels,
                                  int max_disp, int height, int width, int out_halo, void* stream);
+
+/* Backward of s3r_cost_volume_forward on the plain volume (out_halo 0): grad_volume (B, 2C, D, H, W) fp32, plain and contiguous, no halo
+ * (what the adjoint layer's forward of the first 3D convolution writes); grad_left and grad_right (B, C, H, W).  With gv = grad_volume,
+ * n_L(w) = min(D, w + 1) and n_R(w) = min(D, W - w):
+ *   grad_left [b,c,h,w] = sum_{d = 0 .. n_L(w)-1} ( gv[b,  c,d,h,w] - gv[b,C+c,d,h,w-d] )
+ *   grad_right[b,c,h,w] = sum_{d = 0 .. n_R(w)-1} ( gv[b,C+c,d,h,w] - gv[b,  c,d,h,w+d] )
+ * Order, which IS the contract (bit for bit): per output element and per d the difference t_d is ONE fp32 subtraction; the accumulator
+ * starts AS t_0 (not as +0.0); t_1, t_2, ... are added one at a time in ascending d, each add rounded once; nothing is fused into an FMA and
+ * nothing is reassociated.  Every output is its own sequential sum: no cross-lane reduction, no atomics, no scratch — so the bits do not
+ * depend on the run, on an address, on the batch a sample appears in or on the launch shape (a sample of a batch has, bit for bit, the
+ * result of the B = 1 call on it).
+ * Structural zeros are not read into the arithmetic: the positions of grad_volume that the forward writes as the constant 0 — left slab
+ * w < d, right slab w + d >= W, every plane d >= W — appear in neither sum and are never loaded, so a NaN or an infinity there changes no
+ * output bit (they are skipped, not multiplied by a mask: 0 * NaN is NaN).  A NaN or infinity at any other position propagates through
+ * exactly this arithmetic: it reaches the outputs whose sums contain that position — gv[b,c,d,h,w] is in grad_left[b,c,h,w] and in
+ * grad_right[b,c,h,w-d]; gv[b,C+c,d,h,w] is in grad_right[b,c,h,w] and in grad_left[b,c,h,w+d] — and no other.
+ * grad_left or grad_right may be NULL: that side is not computed and the other keeps the bits of the full call; both NULL is
+ * S3R_ERR_INVALID.  batch >= 0 (0 launches nothing and returns S3R_OK); channels, max_disp, height, width >= 1; the shapes
+ * s3r_cost_volume_forward refuses are refused here too (a feature plane pair 2 H W floats beyond 64 KiB: no forward can have written such a
+ * volume; this kernel itself uses no LDS); grad_volume < 2^31 elements.  Outputs are overwritten, never accumulated into.  4-byte alignment
+ * for every argument (all accesses are single dwords).  Nothing is enqueued when the call is refused.  One kernel launch.
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new data in the same buffers).
+ * Profiler: ONE record of family 3, tag 1; `flops` = 2 per summed term (one subtraction, one add) of every side computed; `bytes` = one read
+ * of grad_volume and one write of each gradient asked for: 4 B (2 C D H W + 2 C H W) with both. */
+int s3r_cost_volume_backward(const float* grad_volume, float* grad_left, float* grad_right, int batch, int channels,
+                             int max_disp, int height, int width, void* hip_stream);
 
 /* y[b][o] = act(sum_i x[b][i] w[o][i] + bias[o]); w in torch Linear layout (no packing).  `scratch` holds the
  * split-K partial sums (s3r_linear_scratch_elems floats; reduced in a fixed order: deterministic). */

@@ -79,6 +79,8 @@ SIGNATURES = {
     "s3r_conv_wino_input_layout": (C.c_int, [C.POINTER(ConvDesc)]),
     "s3r_cost_volume_forward_wino2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_int, C.c_void_p]),
+    "s3r_cost_volume_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p]),
     "s3r_linear_scratch_elems": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "s3r_linear_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                      C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),

@@ -853,6 +853,30 @@ int s3r_cost_volume_forward_bf16(const void* fl, const void* fr, void* vol, int 
     return S3R_OK;
 }
 
+int s3r_cost_volume_backward(const float* grad_volume, float* grad_left, float* grad_right, int batch, int channels, int max_disp,
+                             int height, int width, void* hip_stream) {
+    if (!grad_left && !grad_right)
+        return fail(S3R_ERR_INVALID, "cost volume backward: grad_left and grad_right are both NULL (either may be: it is not computed)");
+    if (batch < 0 || channels <= 0 || max_disp <= 0 || height <= 0 || width <= 0)
+        return fail(S3R_ERR_INVALID, "cost volume backward dims must be positive (batch >= 0)");
+    const int64_t hw = (int64_t)height * width;
+    if (2 * hw * 4 > 64 * 1024)      // the forward's domain: a gradient exists for the volumes the forward can write
+        return fail(S3R_ERR_INVALID, "feature plane %dx%d does not fit the forward's LDS staging", height, width);
+    const int64_t vol = (int64_t)batch * 2 * channels * max_disp * hw;
+    if (vol >= kMaxElems) return fail(S3R_ERR_INVALID, "cost volume gradient too large for one call: split the batch");
+    if (batch == 0) return S3R_OK;
+    if (!grad_volume) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    hipStream_t s = (hipStream_t)hip_stream;
+    const double dn = max_disp < width ? max_disp : width;
+    const double terms = dn * (dn + 1.0) / 2.0 + (width - dn) * dn;      // sum over w of n_L(w) = sum over w of n_R(w)
+    const double sides = (grad_left ? 1.0 : 0.0) + (grad_right ? 1.0 : 0.0);
+    const double rows = (double)batch * channels * height;
+    ProfScope ps(s, F_COSTVOL, 1, 2.0 * sides * rows * terms, 4.0 * ((double)vol + sides * rows * width));
+    hipError_t e = s3r::launch_cost_volume_backward(grad_volume, grad_left, grad_right, batch, channels, max_disp, height, width, s);
+    if (e != hipSuccess) return hip_fail(e, "cost volume backward launch");
+    return S3R_OK;
+}
+
 int64_t s3r_linear_scratch_elems(int batch, int cin, int cout) {
     if (batch <= 0 || cin <= 0 || cout <= 0) return fail(S3R_ERR_INVALID, "linear dims must be positive");
     return s3r::linear_scratch_elems(batch, cin, cout);

@@ -315,6 +315,8 @@ int64_t conv_backward_scratch_elems(const ConvBwdGeo& g, int B, int cout, int64_
 hipError_t launch_conv_backward(const ConvBwdGeo& g, int deconv, const float* x, const float* y, const float* gy, const float* scale,
                                 float* gs, float* gw, float* gshift, int B, int cout, int64_t S, int act, float* scratch, hipStream_t s,
                                 int* launches);
+// s3r_cost_volume_bwd.hip: the cost volume's backward, one thread per (b, c, h, w), d ascending; gl or gr may be NULL (not both)
+hipError_t launch_cost_volume_backward(const float* gv, float* gl, float* gr, int B, int C, int D, int H, int W, hipStream_t s);
 // s3r_voxel_loss.hip: BCELoss's per-element rule with a per-sample sum in a fixed order (loss_sum or loss_elem may be NULL), and its
 // elementwise gradient
 hipError_t launch_voxel_bce(const float* pred, const float* target, float* loss_sum, float* loss_elem, int B, int64_t V,

@@ -412,6 +412,23 @@ class _HipChain(nn.Module):
                                                 # timings would not count; the hand-off measured slower)
     _TUNE_KSPLITS = (1, 2, 4, 8)
 
+    def _differentiable_layers(self, x: torch.Tensor, first: int, stop: int) -> torch.Tensor:
+        """Layers first .. stop - 1 of this chain, one `differentiable_conv` each, on this module's OWN parameters.  A block's BatchNorm
+        stays in eval mode and folded: `scale` is `_Block.folded()`'s scale (detached: `bn.weight` is FROZEN on this path, and so are the
+        running statistics); `shift` is folded()'s expression evaluated with torch operations under grad, so grad_shift reaches
+        `bn.bias` and `conv.bias` through torch."""
+        n_in = self._sizes()[first][0]
+        x = _check_input(x, "x", (self._layers[first].cin,) + (n_in,) * 3)
+        for l in self._layers[first:stop]:
+            blk: _Block = getattr(self, l.name)
+            scale, _ = blk.folded()
+            if scale is None:
+                shift = blk.conv.bias
+            else:
+                shift = blk.bn.bias + (blk.conv.bias - blk.bn.running_mean.detach()) * scale
+            x = differentiable_conv(x, blk.conv.weight, scale, shift, l)
+        return x
+
     def _mfma_layers(self):
         return [l for l in self._layers
                 if l.op in ("conv2d", "conv3d", "deconv3d") and l.cin % 16 == 0 and not (l.cout == 1 and l.k == 1)]
@@ -603,6 +620,16 @@ class CostVolume(nn.Module):
                                                        self.max_disp, H, W, 0, _stream_ptr(fl.device)), "cost_volume")
         return vol
 
+    def differentiable(self, feat_left: torch.Tensor, feat_right: torch.Tensor) -> torch.Tensor:
+        """`forward` recorded for autograd on the two feature maps: the plain (B,2C,D,H,W) volume with the bits of `forward`, and the
+        deterministic `cost_volume_backward` behind it (`differentiable_cost_volume`).  fp32 modules only.  The first step of a
+        decoder fine-tune from the features:
+        `model.decoder.differentiable_tail(model.cost_volume.differentiable(fl, fr), start="v1")`."""
+        if self.precision != "fp32":
+            raise RuntimeError(f"CostVolume.differentiable is implemented for fp32 models only (this one is {self.precision}): the "
+                               "cost-volume backward kernel reads fp32 tensors")
+        return differentiable_cost_volume(feat_left, feat_right, self.max_disp)
+
 
 def _check_wino_planes(v: torch.Tensor, layout: int = _lib.LAYOUT_WINO_H) -> torch.Tensor:
     if layout == _lib.LAYOUT_WINO_DH:
@@ -687,18 +714,7 @@ class Decoder(_HipChain):
         self._fp32_only("Decoder.differentiable_features")
         if start not in self.names[:-1]:
             raise RuntimeError(f"start must be one of {self.names[:-1]}, got {start!r}")
-        first = self.names.index(start)
-        n_in = self._sizes()[first][0]
-        x = _check_input(x, "x", (self._layers[first].cin,) + (n_in,) * 3)
-        for l in self._layers[first:-1]:
-            blk: _Block = getattr(self, l.name)
-            scale, _ = blk.folded()
-            if scale is None:
-                shift = blk.conv.bias
-            else:
-                shift = blk.bn.bias + (blk.conv.bias - blk.bn.running_mean.detach()) * scale
-            x = differentiable_conv(x, blk.conv.weight, scale, shift, l)
-        return x
+        return self._differentiable_layers(x, self.names.index(start), len(self._layers) - 1)
 
     def differentiable_tail(self, x: torch.Tensor, start: str = "d3") -> torch.Tensor:
         """`differentiable_head(differentiable_features(x, start))`: layers `start` .. d4 under autograd, (B,32,32,32) occupancy out.
@@ -731,6 +747,18 @@ class VolumeEncoder(_HipChain):
         else:
             x = _check_input(volume_padded, "volume_padded", (2 * spec.FEAT_C,) + n)
         return self._run(x, None, in_halo=halo)
+
+    def differentiable_features(self, x: torch.Tensor, start: str = "v1") -> torch.Tensor:
+        """Layers `start` .. v6 recorded for autograd on this module's own parameters, by the loop of `Decoder.differentiable_features`
+        (`bn.weight` frozen, `bn.bias` and `conv.bias` reached through the folded shift): x is `start`'s input — for "v1" the plain
+        (B,64,28,28,28) volume `CostVolume.differentiable` returns —, the result the (B,512,4,4,4) latent
+        `PointHead.differentiable` reads.  fp32 models only."""
+        if self.precision != "fp32":
+            raise RuntimeError(f"VolumeEncoder.differentiable_features is implemented for fp32 models only (this one is "
+                               f"{self.precision}): the conv backward kernels read fp32 tensors")
+        if start not in self.names:
+            raise RuntimeError(f"start must be one of {self.names}, got {start!r}")
+        return self._differentiable_layers(x, self.names.index(start), len(self._layers))
 
 
 class PointHead(_HipChain):
@@ -765,7 +793,7 @@ READOUTS = ("wta", "soft")
 
 
 class _DisparityMixin:
-    """`disparity()` for the networks that hold an `encoder` and a `cost_volume`."""
+    """`disparity()` and `stereo_features()` for the networks that hold an `encoder` and a `cost_volume`."""
 
     disparity_temperature = DISPARITY_TEMPERATURE      # what disparity(readout="soft") uses when temperature is None
 
@@ -819,6 +847,28 @@ class _DisparityMixin:
             feats = self.encoder.forward_pair(l, r)            # fp32 NCHW, or the bf16 channels-last features as they are
             parts.append(disparity_soft(feats[:b], feats[b:], self.cost_volume.max_disp, tau, size, scale, confidence))
         return tuple(p[0] if len(parts) == 1 else torch.cat(p, 0) for p in zip(*parts))
+
+    @torch.no_grad()
+    def stereo_features(self, left: torch.Tensor, right: torch.Tensor):
+        """(feat_left, feat_right), (B,32,28,28) fp32 each: the FROZEN encoder without a graph — the two maps `forward` feeds the cost
+        volume, through the same `encoder.forward_pair` per chunk of MAX_CHUNK pairs.  Leaves for a decoder fine-tune that wants gradients
+        with respect to the features: `fl.requires_grad_()`, then `cost_volume.differentiable(fl, fr)`.  fp32 models only."""
+        if self.precision != "fp32":
+            raise RuntimeError(f"stereo_features is implemented for fp32 models only (this one is {self.precision}): the cost-volume "
+                               "backward kernel reads fp32 tensors")
+        left = _check_render(left, "left")
+        right = _check_render(right, "right")
+        if left.shape[0] != right.shape[0]:
+            raise RuntimeError("left and right batch sizes differ")
+        fls, frs = [], []
+        for s in range(0, max(left.shape[0], 1), MAX_CHUNK):
+            l, r = left[s:s + MAX_CHUNK], right[s:s + MAX_CHUNK]
+            b = l.shape[0]
+            feats = self.encoder.forward_pair(l, r)              # (2b,32,28,28): left batch, then right batch
+            fls.append(feats[:b]), frs.append(feats[b:])
+        if len(fls) == 1:
+            return fls[0].clone(), frs[0].clone()                # (own tensors: the chain's output buffer is not the caller's)
+        return torch.cat(fls, 0), torch.cat(frs, 0)
 
 
 class Stereo2Voxel(_DisparityMixin, nn.Module):
@@ -1541,6 +1591,61 @@ def differentiable_conv(x: torch.Tensor, weight: torch.Tensor, scale: Optional[t
     `conv_backward`, called with exactly the sides autograd needs (`needs_input_grad` of x, weight and shift).  `scale` is frozen: its
     gradient is `None` (a folded BatchNorm scale: `bn.weight` is not trained through this path)."""
     return _ConvFunction.apply(x, weight, scale, shift, layer)
+
+
+@torch.no_grad()
+def cost_volume_backward(grad_volume: torch.Tensor, need_left: bool = True, need_right: bool = True):
+    """(grad_left, grad_right), (B,C,H,W) each and `None` for the side not asked for, of the plain cost volume for its output gradient
+    grad_volume (B,2C,D,H,W): ONE `s3r_cost_volume_backward` call.  Every element is its own sequential fp32 sum in ascending d (no
+    atomics: the same bits on every run and for every batch a sample appears in); the volume's structural zeros are never read."""
+    if not (need_left or need_right):
+        raise RuntimeError("cost_volume_backward needs need_left or need_right")
+    if not isinstance(grad_volume, torch.Tensor) or grad_volume.dim() != 5 or grad_volume.shape[1] % 2 or grad_volume.shape[1] == 0:
+        raise RuntimeError(f"cost_volume_backward expects grad_volume (B, 2C, D, H, W), got {tuple(getattr(grad_volume, 'shape', ()))}")
+    gv = _check_input(grad_volume.detach(), "grad_volume", grad_volume.shape[1:])
+    B, C2, D, H, W = gv.shape
+    if min(D, H, W) < 1:
+        raise RuntimeError(f"cost_volume_backward: D, H and W must be positive, got {tuple(gv.shape)}")
+    gl = torch.empty((B, C2 // 2, H, W), dtype=torch.float32, device=gv.device) if need_left else None
+    gr = torch.empty((B, C2 // 2, H, W), dtype=torch.float32, device=gv.device) if need_right else None
+    if B == 0:
+        return gl, gr
+    _lib.check(_lib.load().s3r_cost_volume_backward(gv.data_ptr(), None if gl is None else gl.data_ptr(),
+                                                    None if gr is None else gr.data_ptr(), B, C2 // 2, D, H, W,
+                                                    _stream_ptr(gv.device)), "cost volume backward")
+    return gl, gr
+
+
+class _CostVolumeFunction(torch.autograd.Function):
+    """the plain `s3r_cost_volume_forward` (halo 0) with `cost_volume_backward` as its derivative; saves nothing (the operator is linear)"""
+
+    @staticmethod
+    def forward(ctx, feat_left, feat_right, max_disp):
+        if feat_left.shape != feat_right.shape or feat_left.dim() != 4:
+            raise RuntimeError(f"feature maps must both be (B,C,H,W), got {tuple(feat_left.shape)} and {tuple(feat_right.shape)}")
+        fl = _check_input(feat_left.detach(), "feat_left", feat_left.shape[1:])
+        fr = _check_input(feat_right.detach(), "feat_right", feat_left.shape[1:])
+        B, Cc, H, W = fl.shape
+        vol = torch.empty((B, 2 * Cc, int(max_disp), H, W), dtype=torch.float32, device=fl.device)
+        if B:
+            _lib.check(_lib.load().s3r_cost_volume_forward(fl.data_ptr(), fr.data_ptr(), vol.data_ptr(), B, Cc, int(max_disp), H, W, 0,
+                                                           _stream_ptr(fl.device)), "cost_volume")
+        return vol
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_volume):
+        need_l, need_r = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_l or need_r):
+            return None, None, None
+        gl, gr = cost_volume_backward(grad_volume.contiguous().float(), need_l, need_r)
+        return gl, gr, None
+
+
+def differentiable_cost_volume(feat_left: torch.Tensor, feat_right: torch.Tensor, max_disp: int = spec.MAX_DISP) -> torch.Tensor:
+    """The plain fp32 cost volume (B,2C,D,H,W) recorded for autograd: the value has the bits of `CostVolume.forward` (the same kernel call),
+    the backward is `cost_volume_backward`, called with exactly the sides autograd needs (`needs_input_grad` of the two maps)."""
+    return _CostVolumeFunction.apply(feat_left, feat_right, max_disp)
 
 
 @torch.no_grad()
