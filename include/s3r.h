@@ -30,6 +30,8 @@
  *                                           one pass over the grid, fixed summation orders, no atomics   (README.md:77)
  *   s3r_conv_backward (+ s3r_conv_adjoint_desc) torch autograd's backward of a conv3d / ConvTranspose3d + BN + activation block of the voxel
  *                                           decoder: what `python3 runner.py` runs behind the loss for the up-path (README.md:77)
+ *   s3r_batchnorm_train_forward / _backward torch.nn.BatchNorm2d/3d in TRAINING mode (batch statistics) + activation and its autograd
+ *                                           backward: what trains bn.weight / bn.bias of the conv + BN + ReLU blocks   (README.md:77)
  *   s3r_disparity_wta, s3r_disparity_epe    predicted left / right disparity and its end-point error
  *                                           against the disp_%02d_{l,r}.exr ground truth (README.md:75-76)
  *   s3r_disparity_soft                      the same prediction as a sub-pixel soft-argmin, upsampled to the
@@ -75,7 +77,8 @@ extern "C" {
  * s3r_disparity_soft and s3r_disparity_metrics were added later as new entry points only (no struct or existing signature changed):
  * the version stays 8.  s3r_chamfer_backward and s3r_linear_backward (+ its scratch query) likewise; s3r_voxel_bce_forward,
  * s3r_voxel_bce_backward and s3r_head_backward (+ its scratch query) likewise; s3r_conv_adjoint_desc and s3r_conv_backward (+ its scratch
- * query) likewise; s3r_cost_volume_backward likewise: new entry points only, the version stays 8. */
+ * query) likewise; s3r_cost_volume_backward likewise; s3r_batchnorm_train_forward and s3r_batchnorm_train_backward (+ their scratch queries)
+ * likewise: new entry points only, the version stays 8. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -541,6 +544,66 @@ int s3r_conv_adjoint_desc(const s3r_conv_desc* d, s3r_conv_desc* adj);
 int64_t s3r_conv_backward_scratch_elems(const s3r_conv_desc* d);
 int s3r_conv_backward(const s3r_conv_desc* d, const float* x, const float* y, const float* grad_y, const float* scale, float* gs,
                       float* grad_w, float* grad_shift, float* scratch, int64_t scratch_elems, void* hip_stream);
+
+/* Train-mode BatchNorm (batch statistics) + activation on z (B,C,S) fp32, plain and contiguous; S (`positions`) is the product of the
+ * spatial extents, so one entry serves 2D and 3D layers.  gamma, beta, save_mean, save_var, save_invstd, grad_gamma, grad_beta are (C).
+ * With N = B S and nf = (float)N (rounded to nearest when N > 2^24), per channel c, in fp32, EVERY operation rounded on its own — the
+ * product is rounded, then the add: nothing is fused, so a numpy restatement is exact:
+ *   mean[c]   = (sum_{b,s} z) / nf
+ *   var[c]    = (sum_{b,s} d * d) / nf,  d = z - mean[c], d * d rounded before the add: the BIASED variance, in two passes over z — there
+ *               is no sum of z^2, so data with |mean| >> std do not cancel;
+ *   invstd[c] = 1.f / sqrtf(var[c] + eps)          (the division and the square root are IEEE-correct)
+ *   xhat = (z - mean[c]) * invstd[c];  t = xhat * gamma[c];  u = t + beta[c];  y = act(u)
+ *   act: S3R_ACT_NONE: u;  S3R_ACT_RELU: (u < 0.f) ? 0.f : u (a NaN stays a NaN);  S3R_ACT_SIGMOID: 1.f / (1.f + exp(-u)) with the fast
+ *   exponential of the forward kernels (not correctly rounded: y is then NOT bit for bit against a restatement; the rest is).  Anything else
+ *   is S3R_ERR_INVALID.
+ * s3r_batchnorm_train_backward takes the forward's z, y, save_mean, save_invstd and the output gradient grad_y (B,C,S):
+ *   g the pre-activation gradient, s3r_linear_backward's rule:  none: g = grad_y;  ReLU: g = (y > 0.f) ? grad_y : 0.f (a NaN y gives 0);
+ *   sigmoid: t = 1 - y; u = y * t; g = grad_y * u;
+ *   grad_beta[c]  = sum_{b,s} g
+ *   grad_gamma[c] = sum_{b,s} g * xhat,  xhat = (z - mean[c]) * invstd[c] recomputed exactly as in the forward; the product is rounded, then added;
+ *   m1 = grad_beta[c] / nf;  m2 = grad_gamma[c] / nf;  a = gamma[c] * invstd[c];  p = xhat * m2;  q = g - m1;  r = q - p;  grad_z = a * r.
+ * Summation order of the four sums (z; d * d; g; g * xhat), which IS the contract (bit for bit) — s3r_head_backward's, with a (b, c) row in
+ * place of a sample:
+ *   - a row's S positions are cut into chunks of 512 consecutive positions (the last may be short; missing positions count as +0.0);
+ *   - within a chunk, lane L (0..63) owns the 8 positions 256 j + 4 L + i (j = 0, 1; i = 0..3) and adds their terms in ascending position
+ *     to a partial that starts as +0.0; the 64 partials are combined by the halving tree v[L] = v[L] + v[L + o] for L < o,
+ *     o = 32, 16, 8, 4, 2, 1; v[0] is the chunk's sum;
+ *   - per (b, c) row, the chunk sums are added in ascending chunk order into a partial that starts as chunk 0's sum: a function of S only;
+ *   - per channel, the rows' partials are added into one accumulator in ascending b, starting from sample 0's.
+ * The chunk sums go through `scratch`.  No atomics: the bits depend on the shape and the data only — not on the run, not on an address
+ * (4-byte alignment suffices for every argument) and not on the scratch's contents on entry.  UNLIKE the other training entries, a sample's
+ * result DOES depend on the batch it is in: mean and var are statistics of the whole batch, and y, grad_z and both sums inherit that.
+ * Non-finite input: a NaN or +-inf in z poisons ITS channel's statistics — mean is NaN (+-inf for an inf), var and invstd are NaN — and with
+ * them every y, grad_gamma and grad_z of that channel is NaN (grad_beta reads y and grad_y only); no other channel changes a bit.  It is not
+ * an error.
+ * The forward's five outputs are all required.  grad_z, grad_gamma and grad_beta may each be NULL: that output is not computed and costs no
+ * write, and the computed ones keep the bits of the full call; grad_z needs both sums, which then live in scratch; all three NULL is
+ * S3R_ERR_INVALID.  y may be NULL when act is none (y NULL with ReLU or sigmoid: S3R_ERR_INVALID); z, save_mean and save_invstd may be NULL
+ * when grad_gamma and grad_z both are (z is then not read); gamma may be NULL when grad_z is.  Outputs are overwritten, never accumulated into.
+ * batch >= 0 (0 launches nothing, writes nothing and returns S3R_OK); channels, positions >= 1; N >= 2 (one value per channel has no
+ * variance: torch refuses it too); every tensor < 2^31 elements and < 4 GiB: anything else is S3R_ERR_INVALID before anything is enqueued.
+ * `scratch`: s3r_batchnorm_train_forward_scratch_elems = channels * batch * ceil(positions / 512) floats (both statistics passes use them in
+ * turn); s3r_batchnorm_train_backward_scratch_elems = 2 * channels * batch * ceil(positions / 512) + 2 * channels floats; functions of the
+ * shape only — never of the device, the activation or the outputs asked for —, monotone in batch; a shorter (or NULL) one is
+ * S3R_ERR_WORKSPACE.
+ * Launches.  Forward 5: the z sums, their finish (mean), the d * d sums, their finish (var, invstd), the normalise pass — z is read three
+ * times and y written once.  Backward 3: the two sums in one pass, their finish, the grad_z pass — z, y and grad_y are read twice and
+ * grad_z written once; 2 launches without grad_z.  A finish is one wave per channel; it is not folded into the pass that consumes it (every
+ * wave of that pass would re-add the channel's batch * ceil(positions / 512) chunk sums to stream 512 positions).
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new data in the same buffers).
+ * Profiler: ONE record per call, family 2, tag 2 (forward) / 3 (backward), whose `launches` is the number of kernel launches above;
+ * `flops` = 0; `bytes` = the tensor traffic the launches need: forward 4 N C * 4 B (+ the (C) vectors), backward 4 B * N C * (reads of
+ * grad_y, y unless act is none, z unless only grad_beta is computed — twice with grad_z — + the grad_z write). */
+int64_t s3r_batchnorm_train_forward_scratch_elems(int batch, int channels, int64_t positions);
+int s3r_batchnorm_train_forward(const float* z, const float* gamma, const float* beta, float eps, int act, float* y, float* save_mean,
+                                float* save_var, float* save_invstd, int batch, int channels, int64_t positions, float* scratch,
+                                int64_t scratch_elems, void* hip_stream);
+int64_t s3r_batchnorm_train_backward_scratch_elems(int batch, int channels, int64_t positions);
+int s3r_batchnorm_train_backward(const float* z, const float* y, const float* grad_y, const float* gamma, const float* save_mean,
+                                 const float* save_invstd, int act, float* grad_z, float* grad_gamma, float* grad_beta, int batch,
+                                 int channels, int64_t positions, float* scratch, int64_t scratch_elems, void* hip_stream);
 
 /* Disparity read-out: winner-take-all over the shift-and-diff costs of the cost volume (same features, same
  * |L - R shifted| costs, volume never materialised).  feat_* (B,C,H,W) fp32; disp_* (B,H,W) fp32, integer-valued,

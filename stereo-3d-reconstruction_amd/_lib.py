@@ -97,6 +97,12 @@ SIGNATURES = {
     "s3r_head_backward_scratch_elems": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
     "s3r_head_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "s3r_batchnorm_train_forward_scratch_elems": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+    "s3r_batchnorm_train_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "s3r_batchnorm_train_backward_scratch_elems": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+    "s3r_batchnorm_train_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "s3r_conv_adjoint_desc": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc)]),
     "s3r_conv_backward_scratch_elems": (C.c_int64, [C.POINTER(ConvDesc)]),
     "s3r_conv_backward": (C.c_int, [C.POINTER(ConvDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

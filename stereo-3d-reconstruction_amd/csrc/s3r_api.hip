@@ -1145,6 +1145,88 @@ int s3r_conv_backward(const s3r_conv_desc* d, const float* x, const float* y, co
     return S3R_OK;
 }
 
+// z / y / grad_z of a train-mode BatchNorm call within the header's limits (< 2^31 elements, < 4 GiB)
+static int bn_dims(int batch, int channels, int64_t positions) {
+    if (batch < 0 || channels <= 0 || positions <= 0)
+        return fail(S3R_ERR_INVALID, "batchnorm dims: batch >= 0, channels > 0 and positions > 0 (batch %d, channels %d, positions %lld)", batch,
+                    channels, (long long)positions);
+    if (positions >= kMaxElems || (int64_t)channels * positions >= kMaxElems || (int64_t)batch * channels * positions >= kMaxElems ||
+        4 * (int64_t)batch * channels * positions >= kMaxBytes)
+        return fail(S3R_ERR_INVALID, "tensor of 4 GiB or more: split the channels");
+    return S3R_OK;
+}
+
+static int bn_act_ok(int act, const char* who) {
+    if (act < S3R_ACT_NONE || act > S3R_ACT_SIGMOID) return fail(S3R_ERR_INVALID, "%s takes none / relu / sigmoid (act %d)", who, act);
+    return S3R_OK;
+}
+
+int64_t s3r_batchnorm_train_forward_scratch_elems(int batch, int channels, int64_t positions) {
+    int rc = bn_dims(batch, channels, positions);
+    if (rc) return rc;
+    return s3r::batchnorm_forward_scratch_elems(batch, channels, positions);
+}
+
+int64_t s3r_batchnorm_train_backward_scratch_elems(int batch, int channels, int64_t positions) {
+    int rc = bn_dims(batch, channels, positions);
+    if (rc) return rc;
+    return s3r::batchnorm_backward_scratch_elems(batch, channels, positions);
+}
+
+int s3r_batchnorm_train_forward(const float* z, const float* gamma, const float* beta, float eps, int act, float* y, float* save_mean,
+                                float* save_var, float* save_invstd, int batch, int channels, int64_t positions, float* scratch,
+                                int64_t scratch_elems, void* hip_stream) {
+    int rc = bn_act_ok(act, "s3r_batchnorm_train_forward");
+    if (rc) return rc;
+    rc = bn_dims(batch, channels, positions);
+    if (rc) return rc;
+    if (batch == 0) return S3R_OK;
+    if ((int64_t)batch * positions < 2)
+        return fail(S3R_ERR_INVALID, "batchnorm: batch statistics need more than one value per channel (batch * positions = 1)");
+    if (!z || !gamma || !beta || !y || !save_mean || !save_var || !save_invstd) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    const int64_t need = s3r::batchnorm_forward_scratch_elems(batch, channels, positions);
+    if (!scratch || scratch_elems < need)
+        return fail(S3R_ERR_WORKSPACE, "batchnorm forward needs %lld floats of scratch (s3r_batchnorm_train_forward_scratch_elems), got %lld",
+                    (long long)need, (long long)(scratch ? scratch_elems : 0));
+    hipStream_t s = (hipStream_t)hip_stream;
+    const double T = (double)batch * channels * (double)positions;
+    ProfScope ps(s, F_HEAD, 2, 0.0, 4.0 * (4.0 * T + 5.0 * channels));
+    hipError_t e = s3r::launch_batchnorm_train_forward(z, gamma, beta, eps, act, y, save_mean, save_var, save_invstd, batch, channels,
+                                                       positions, scratch, s, &ps.launches);
+    if (e != hipSuccess) return hip_fail(e, "batchnorm forward launch");
+    return S3R_OK;
+}
+
+int s3r_batchnorm_train_backward(const float* z, const float* y, const float* grad_y, const float* gamma, const float* save_mean,
+                                 const float* save_invstd, int act, float* grad_z, float* grad_gamma, float* grad_beta, int batch,
+                                 int channels, int64_t positions, float* scratch, int64_t scratch_elems, void* hip_stream) {
+    if (!grad_z && !grad_gamma && !grad_beta)
+        return fail(S3R_ERR_INVALID, "batchnorm backward: grad_z, grad_gamma and grad_beta are all NULL (each may be: it is not computed)");
+    int rc = bn_act_ok(act, "s3r_batchnorm_train_backward");
+    if (rc) return rc;
+    rc = bn_dims(batch, channels, positions);
+    if (rc) return rc;
+    if (batch == 0) return S3R_OK;
+    if ((int64_t)batch * positions < 2)
+        return fail(S3R_ERR_INVALID, "batchnorm: batch statistics need more than one value per channel (batch * positions = 1)");
+    const bool gg = grad_gamma || grad_z;
+    if (!grad_y || (gg && (!z || !save_mean || !save_invstd)) || (grad_z && !gamma)) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    if (act != S3R_ACT_NONE && !y) return fail(S3R_ERR_INVALID, "batchnorm backward: y is NULL (it may be only when act is none)");
+    const int64_t need = s3r::batchnorm_backward_scratch_elems(batch, channels, positions);
+    if (!scratch || scratch_elems < need)
+        return fail(S3R_ERR_WORKSPACE, "batchnorm backward needs %lld floats of scratch (s3r_batchnorm_train_backward_scratch_elems), got %lld",
+                    (long long)need, (long long)(scratch ? scratch_elems : 0));
+    hipStream_t s = (hipStream_t)hip_stream;
+    const double T = (double)batch * channels * (double)positions;
+    const double reads = 1.0 + (act != S3R_ACT_NONE ? 1.0 : 0.0) + (gg ? 1.0 : 0.0);
+    ProfScope ps(s, F_HEAD, 3, 0.0, 4.0 * (T * (grad_z ? 2.0 * reads + 1.0 : reads) + (double)channels * ((gg ? 2.0 : 0.0) + (grad_z ? 1.0 : 0.0) +
+                                                 (grad_gamma ? 1.0 : 0.0) + (grad_beta ? 1.0 : 0.0))));
+    hipError_t e = s3r::launch_batchnorm_train_backward(z, y, grad_y, gamma, save_mean, save_invstd, act, grad_z, grad_gamma, grad_beta, batch,
+                                                        channels, positions, scratch, s, &ps.launches);
+    if (e != hipSuccess) return hip_fail(e, "batchnorm backward launch");
+    return S3R_OK;
+}
+
 int s3r_disparity_wta(const float* feat_l, const float* feat_r, float* disp_l, float* disp_r, int batch, int channels,
                       int height, int width, int max_disp, void* stream) {
     if (!feat_l || !feat_r || !disp_l || !disp_r) return fail(S3R_ERR_INVALID, "null tensor pointer");

@@ -292,6 +292,17 @@ hipError_t launch_head_backward(const float* x, const float* w, const float* sca
                                 float* gw, float* gshift, int B, int C, int64_t S, int act, float* scratch, hipStream_t s,
                                 int* launches);
 int64_t head_backward_scratch_elems(int B, int C, int64_t S);
+// s3r_batchnorm.hip: train-mode BatchNorm on z (B,C,S) with batch statistics: two-pass mean / biased variance, y = act(xhat * gamma + beta),
+// and its backward; fixed summation orders (the head backward's, a (b, c) row in place of a sample), no atomics.  gz, ggamma, gbeta: NULL =
+// not computed (not all three); scratch: batchnorm_{forward,backward}_scratch_elems floats of chunk sums
+hipError_t launch_batchnorm_train_forward(const float* z, const float* gamma, const float* beta, float eps, int act, float* y,
+                                          float* mean, float* var, float* invstd, int B, int C, int64_t S, float* scratch, hipStream_t s,
+                                          int* launches);
+hipError_t launch_batchnorm_train_backward(const float* z, const float* y, const float* gy, const float* gamma, const float* mean,
+                                           const float* invstd, int act, float* gz, float* ggamma, float* gbeta, int B, int C, int64_t S,
+                                           float* scratch, hipStream_t s, int* launches);
+int64_t batchnorm_forward_scratch_elems(int B, int C, int64_t S);
+int64_t batchnorm_backward_scratch_elems(int B, int C, int64_t S);
 // s3r_conv_bwd.hip: backward of one fp32 Conv / ConvTranspose layer except its input gradient (that is the adjoint layer's forward):
 // gs = g * scale, grad_shift in the head backward's order, grad_w as a sliced GEMM whose slabs are added in a fixed order.
 // ConvBwdGeo: the weight-gradient GEMM's tiling, a function of the layer's per-sample geometry only (convbwd_geo; false: no tiling fits)

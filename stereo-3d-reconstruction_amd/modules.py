@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
+import dataclasses
 import os
 import weakref
 from typing import Dict, List, Optional, Sequence
@@ -412,15 +413,23 @@ class _HipChain(nn.Module):
                                                 # timings would not count; the hand-off measured slower)
     _TUNE_KSPLITS = (1, 2, 4, 8)
 
-    def _differentiable_layers(self, x: torch.Tensor, first: int, stop: int) -> torch.Tensor:
+    def _differentiable_layers(self, x: torch.Tensor, first: int, stop: int, batch_stats: bool = False) -> torch.Tensor:
         """Layers first .. stop - 1 of this chain, one `differentiable_conv` each, on this module's OWN parameters.  A block's BatchNorm
         stays in eval mode and folded: `scale` is `_Block.folded()`'s scale (detached: `bn.weight` is FROZEN on this path, and so are the
         running statistics); `shift` is folded()'s expression evaluated with torch operations under grad, so grad_shift reaches
-        `bn.bias` and `conv.bias` through torch."""
+        `bn.bias` and `conv.bias` through torch.
+        batch_stats=True: a layer WITH a BatchNorm runs as torch runs the block in training mode, in two calls —
+        `differentiable_conv(x, conv.weight, None, conv.bias, <the layer with act "none">)`, then
+        `differentiable_batchnorm(z, blk.bn, layer.act)`: batch statistics, gradients to `bn.weight` and `bn.bias`, the running
+        statistics updated.  Layers without a BatchNorm are unchanged."""
         n_in = self._sizes()[first][0]
         x = _check_input(x, "x", (self._layers[first].cin,) + (n_in,) * 3)
         for l in self._layers[first:stop]:
             blk: _Block = getattr(self, l.name)
+            if batch_stats and blk.bn is not None:
+                z = differentiable_conv(x, blk.conv.weight, None, blk.conv.bias, dataclasses.replace(l, act="none"))
+                x = differentiable_batchnorm(z, blk.bn, l.act)
+                continue
             scale, _ = blk.folded()
             if scale is None:
                 shift = blk.conv.bias
@@ -699,7 +708,7 @@ class Decoder(_HipChain):
         blk: _Block = getattr(self, l.name)
         return differentiable_head(x, blk.conv.weight, blk.conv.bias, l.act)
 
-    def differentiable_features(self, x: torch.Tensor, start: str = "d3") -> torch.Tensor:
+    def differentiable_features(self, x: torch.Tensor, start: str = "d3", batch_stats: bool = False) -> torch.Tensor:
         """Layers `start` .. d3 recorded for autograd on this module's OWN parameters: x is `start`'s input (for "d3" the
         (B,128,16,16,16) activation `Stereo2Voxel.trunk_features(l, r, upto="d2")` returns), the result d3's (B,64,32,32,32) output —
         what `features()` returns, with a graph.  Every layer runs as `differentiable_conv`: its kernel's forward under the AUTO
@@ -710,19 +719,22 @@ class Decoder(_HipChain):
         With start = "d3" the value HAS the bits of `features()` (the chain up to d3): measured bit-identical at B = 1, 2 and 5 on an
         MI355X (LAB_NOTES, "Conv backward") and pinned by
         tests/test_conv_backward_gpu.py::test_standalone_d3_forward_has_the_bits_of_the_chain on THIS method's output — both run d3's
-        three-axis Winograd form on the same input, and its launch forms agree bit for bit."""
+        three-axis Winograd form on the same input, and its launch forms agree bit for bit.
+        batch_stats=True trains the blocks as torch trains `nn.ConvTranspose3d + nn.BatchNorm3d + ReLU` in training mode: each BatchNorm
+        layer runs `differentiable_conv` without scale and activation and then `differentiable_batchnorm` (batch statistics;
+        `bn.weight.grad` and `bn.bias.grad` from the HIP backward; running statistics updated).  The value then depends on the batch."""
         self._fp32_only("Decoder.differentiable_features")
         if start not in self.names[:-1]:
             raise RuntimeError(f"start must be one of {self.names[:-1]}, got {start!r}")
-        return self._differentiable_layers(x, self.names.index(start), len(self._layers) - 1)
+        return self._differentiable_layers(x, self.names.index(start), len(self._layers) - 1, batch_stats)
 
-    def differentiable_tail(self, x: torch.Tensor, start: str = "d3") -> torch.Tensor:
+    def differentiable_tail(self, x: torch.Tensor, start: str = "d3", batch_stats: bool = False) -> torch.Tensor:
         """`differentiable_head(differentiable_features(x, start))`: layers `start` .. d4 under autograd, (B,32,32,32) occupancy out.
         d4's standalone kernel agrees with the fused d3 + d4 pass of `forward` to fp32 rounding (`differentiable_head`).  `bn.weight`
-        is frozen (see `differentiable_features`).  The fine-tune step on a frozen trunk:
+        is frozen unless batch_stats=True (see `differentiable_features`).  The fine-tune step on a frozen trunk:
         `VoxelBCELoss()(model.decoder.differentiable_tail(model.trunk_features(l, r, upto="d2")), gt).backward()`."""
         self._fp32_only("Decoder.differentiable_tail")
-        return self.differentiable_head(self.differentiable_features(x, start))
+        return self.differentiable_head(self.differentiable_features(x, start, batch_stats))
 
 
 class VolumeEncoder(_HipChain):
@@ -748,17 +760,18 @@ class VolumeEncoder(_HipChain):
             x = _check_input(volume_padded, "volume_padded", (2 * spec.FEAT_C,) + n)
         return self._run(x, None, in_halo=halo)
 
-    def differentiable_features(self, x: torch.Tensor, start: str = "v1") -> torch.Tensor:
+    def differentiable_features(self, x: torch.Tensor, start: str = "v1", batch_stats: bool = False) -> torch.Tensor:
         """Layers `start` .. v6 recorded for autograd on this module's own parameters, by the loop of `Decoder.differentiable_features`
         (`bn.weight` frozen, `bn.bias` and `conv.bias` reached through the folded shift): x is `start`'s input — for "v1" the plain
         (B,64,28,28,28) volume `CostVolume.differentiable` returns —, the result the (B,512,4,4,4) latent
-        `PointHead.differentiable` reads.  fp32 models only."""
+        `PointHead.differentiable` reads.  fp32 models only.  batch_stats=True: every BatchNorm layer in training form, as
+        `Decoder.differentiable_features` describes."""
         if self.precision != "fp32":
             raise RuntimeError(f"VolumeEncoder.differentiable_features is implemented for fp32 models only (this one is "
                                f"{self.precision}): the conv backward kernels read fp32 tensors")
         if start not in self.names:
             raise RuntimeError(f"start must be one of {self.names}, got {start!r}")
-        return self._differentiable_layers(x, self.names.index(start), len(self._layers))
+        return self._differentiable_layers(x, self.names.index(start), len(self._layers), batch_stats)
 
 
 class PointHead(_HipChain):
@@ -1591,6 +1604,127 @@ def differentiable_conv(x: torch.Tensor, weight: torch.Tensor, scale: Optional[t
     `conv_backward`, called with exactly the sides autograd needs (`needs_input_grad` of x, weight and shift).  `scale` is frozen: its
     gradient is `None` (a folded BatchNorm scale: `bn.weight` is not trained through this path)."""
     return _ConvFunction.apply(x, weight, scale, shift, layer)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Train-mode BatchNorm (batch statistics) + activation: s3r_batchnorm_train_forward / _backward
+def _check_bn(z, who):
+    if not isinstance(z, torch.Tensor) or z.dim() < 2:
+        raise RuntimeError(f"{who} expects z (B, C, ...), got {tuple(getattr(z, 'shape', ()))}")
+    z = _check_input(z.detach(), "z", z.shape[1:])
+    S = 1
+    for n in z.shape[2:]:
+        S *= n
+    if z.shape[1] == 0 or S == 0:
+        raise RuntimeError(f"{who} needs non-empty channels and positions")
+    if z.shape[0] * S < 2:
+        raise RuntimeError(f"{who}: batch statistics need more than one value per channel, got z {tuple(z.shape)}")
+    return z, S
+
+
+@torch.no_grad()
+def batchnorm_train_forward(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, act: str = "none"):
+    """(y, mean, var, invstd) of train-mode BatchNorm + activation on z (B,C,...) (`s3r_batchnorm_train_forward`): per channel the batch
+    mean and the BIASED variance in two passes, invstd = 1 / sqrt(var + eps), y = act(((z - mean) * invstd) * gamma + beta) with nothing
+    fused; gamma, beta (C); act "none", "relu" or "sigmoid".  Fixed summation orders, no atomics: the same bits on every run.  A sample's
+    result depends on the batch it is in.  Records no graph (`differentiable_batchnorm` does)."""
+    if act not in _LINEAR_ACTS:
+        raise RuntimeError(f"batchnorm_train_forward: act must be one of {_LINEAR_ACTS}, got {act!r}")
+    z, S = _check_bn(z, "batchnorm_train_forward")
+    B, ch, dev = z.shape[0], z.shape[1], z.device
+    ga = _check_channel_vector(gamma, ch, dev, "batchnorm_train_forward", "gamma")
+    be = _check_channel_vector(beta, ch, dev, "batchnorm_train_forward", "beta")
+    y = torch.empty_like(z)
+    mean, var, invstd = (torch.empty((ch,), dtype=torch.float32, device=dev) for _ in range(3))
+    lib = _lib.load()
+    need = _lib.check(lib.s3r_batchnorm_train_forward_scratch_elems(B, ch, S), "batchnorm forward scratch query")
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    _lib.check(lib.s3r_batchnorm_train_forward(z.data_ptr(), ga.data_ptr(), be.data_ptr(), float(eps), _lib.ACT[act], y.data_ptr(),
+                                               mean.data_ptr(), var.data_ptr(), invstd.data_ptr(), B, ch, S, scratch.data_ptr(),
+                                               scratch.numel(), _stream_ptr(dev)), "batchnorm forward")
+    return y, mean, var, invstd
+
+
+@torch.no_grad()
+def batchnorm_train_backward(z: torch.Tensor, y: Optional[torch.Tensor], grad_y: torch.Tensor, gamma: torch.Tensor, mean: torch.Tensor,
+                             invstd: torch.Tensor, act: str, need_z: bool = True, need_gamma: bool = True, need_beta: bool = True):
+    """(grad_z, grad_gamma, grad_beta) of `batchnorm_train_forward` for the output gradient grad_y (the shape of z), `None` for the sides
+    not asked for (`s3r_batchnorm_train_backward`): z, y, mean and invstd are the forward's (y may be None when act is "none").  One pass
+    for the two sums, a finish, one pass for grad_z; fixed summation orders, no atomics.  A side that is not asked for is not written."""
+    if act not in _LINEAR_ACTS:
+        raise RuntimeError(f"batchnorm_train_backward: act must be one of {_LINEAR_ACTS}, got {act!r}")
+    if not (need_z or need_gamma or need_beta):
+        raise RuntimeError("batchnorm_train_backward needs need_z, need_gamma or need_beta")
+    z, S = _check_bn(z, "batchnorm_train_backward")
+    B, ch, dev = z.shape[0], z.shape[1], z.device
+    gy = _check_input(grad_y, "grad_y", z.shape[1:])
+    if gy.shape[0] != B:
+        raise RuntimeError(f"grad_y must hold {B} samples, got {gy.shape[0]}")
+    yy = None
+    if act != "none":
+        if y is None:
+            raise RuntimeError(f"batchnorm_train_backward: act {act!r} needs the layer's output y")
+        yy = _check_input(y.detach(), "y", z.shape[1:])
+        if yy.shape[0] != B:
+            raise RuntimeError(f"y must hold {B} samples, got {yy.shape[0]}")
+    ga, mu, iv = (_check_channel_vector(v, ch, dev, "batchnorm_train_backward", n)
+                  for v, n in ((gamma, "gamma"), (mean, "mean"), (invstd, "invstd")))
+    gz = torch.empty_like(z) if need_z else None
+    gg = torch.empty((ch,), dtype=torch.float32, device=dev) if need_gamma else None
+    gb = torch.empty((ch,), dtype=torch.float32, device=dev) if need_beta else None
+    lib = _lib.load()
+    need = _lib.check(lib.s3r_batchnorm_train_backward_scratch_elems(B, ch, S), "batchnorm backward scratch query")
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    ptr = [None if t is None else t.data_ptr() for t in (gz, gg, gb)]
+    _lib.check(lib.s3r_batchnorm_train_backward(z.data_ptr(), None if yy is None else yy.data_ptr(), gy.data_ptr(), ga.data_ptr(),
+                                                mu.data_ptr(), iv.data_ptr(), _lib.ACT[act], *ptr, B, ch, S, scratch.data_ptr(),
+                                                scratch.numel(), _stream_ptr(dev)), "batchnorm backward")
+    return gz, gg, gb
+
+
+class _BatchNormTrainFunction(torch.autograd.Function):
+    """`batchnorm_train_forward` with `batchnorm_train_backward` as its derivative; saves z, gamma, y, mean and invstd.  mean and var
+    are returned for the running statistics and carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, eps, act):
+        y, mean, var, invstd = batchnorm_train_forward(z, gamma, beta, eps, act)
+        ctx.act = act
+        ctx.save_for_backward(z, gamma, y, mean, invstd)
+        ctx.mark_non_differentiable(mean, var)
+        return y, mean, var
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y, _gmean, _gvar):
+        z, gamma, y, mean, invstd = ctx.saved_tensors
+        need_z, need_gamma, need_beta = ctx.needs_input_grad[:3]
+        if not (need_z or need_gamma or need_beta):
+            return None, None, None, None, None
+        gz, gg, gb = batchnorm_train_backward(z, y, grad_y.contiguous().float(), gamma, mean, invstd, ctx.act, need_z, need_gamma, need_beta)
+        return gz, gg, gb, None, None
+
+
+def differentiable_batchnorm(z: torch.Tensor, bn: nn.Module, act: str = "none") -> torch.Tensor:
+    """act(bn(z)) of an affine `nn.BatchNorm2d` / `nn.BatchNorm3d` (any `_BatchNorm`) with BATCH statistics — torch's training mode,
+    whatever `bn.training` says — recorded for autograd: `batchnorm_train_forward`'s bits, with the deterministic backward
+    `batchnorm_train_backward` called with exactly the sides autograd needs (`needs_input_grad` of z, `bn.weight`, `bn.bias`).  When
+    `bn.track_running_stats` is set the running statistics and `num_batches_tracked` are updated as torch updates them: with
+    `bn.momentum` (None: the cumulative average 1 / num_batches_tracked) and the UNBIASED variance var * N / (N - 1), in torch operations
+    on the (C) vectors under no_grad."""
+    if not isinstance(bn, nn.modules.batchnorm._BatchNorm) or bn.weight is None or bn.bias is None:
+        raise RuntimeError("differentiable_batchnorm takes an affine nn.BatchNorm1d / 2d / 3d module")
+    if not isinstance(z, torch.Tensor) or z.dim() < 2 or z.shape[1] != bn.num_features:
+        raise RuntimeError(f"differentiable_batchnorm expects z (B, {bn.num_features}, ...), got {tuple(getattr(z, 'shape', ()))}")
+    y, mean, var = _BatchNormTrainFunction.apply(z, bn.weight, bn.bias, float(bn.eps), act)
+    if bn.track_running_stats and bn.running_mean is not None:
+        with torch.no_grad():
+            n = z.numel() // z.shape[1]
+            bn.num_batches_tracked += 1
+            f = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else float(bn.momentum)
+            bn.running_mean.mul_(1.0 - f).add_(mean, alpha=f)
+            bn.running_var.mul_(1.0 - f).add_(var * (n / (n - 1.0)), alpha=f)
+    return y
 
 
 @torch.no_grad()
