@@ -164,7 +164,12 @@ typedef enum s3r_layout { S3R_LAYOUT_PLAIN = 0, S3R_LAYOUT_WINO_H = 2, S3R_LAYOU
  *                      and H, Conv2d k3 s1 p1 as F(4,3) x F(4,3) over H and W, Conv3d k4 s1 p0 as F(2,4) x F(2,4); in_halo = pad;
  *                      4 / 5 force its class-parallel / semi-fused launch form: same bits) — another algorithm, other bits than
  *                      the one-axis kernel; AUTO takes it for every stride-1 layer that has it and an edge <= 28 (e6, e7, v1, v3,
- *                      v5, v6 of this network).
+ *                      v5, v6 of this network).  Two of its finish kernels stage PADDED output planes in 64 KiB of LDS, which bounds
+ *                      the edge n together with out_halo: the Conv2d form (tile 3, 4, 5) serves n <= 124 with n + 2 out_halo <= 128
+ *                      (one plane), the semi-fused Conv3d form (tile 5) n <= 60 with n + 2 out_halo <= 64 (four slices).  The
+ *                      class-parallel Conv3d form (tile 4) has no such bound, and the library's own pick (tile 3 or -1) takes it
+ *                      for a Conv3d outside the semi-fused form's.  A descriptor outside these bounds is refused like any other
+ *                      the layer has no form for: S3R_ERR_INVALID from s3r_conv_scratch_elems and s3r_conv_forward, nothing enqueued.
  * A call whose scratch is smaller than s3r_conv_scratch_elems says for the RESOLVED algorithm fails with S3R_ERR_WORKSPACE; it
  * is never answered with the other kernel's bits. */
 typedef enum s3r_algo { S3R_ALGO_AUTO = 0, S3R_ALGO_DIRECT = 1, S3R_ALGO_WINOGRAD = 2 } s3r_algo;
@@ -176,10 +181,12 @@ typedef enum s3r_algo { S3R_ALGO_AUTO = 0, S3R_ALGO_DIRECT = 1, S3R_ALGO_WINOGRA
  * (B, C, n+2*halo, ...) tensor whose border is zero and whose interior is the logical (B, C, n, ...)
  * tensor.  `in_halo` / `out_halo` describe the buffers `x` / `y` of s3r_conv_forward.  A layer with
  * padding p (or a ConvTranspose) served by the MFMA kernel needs in_halo >= p (>= 1); kernels write
- * interiors only, so a buffer zeroed once keeps its halo.  Two writers store whole padded rows instead (whole 128-byte lines:
+ * interiors only, so a buffer zeroed once keeps its halo.  Three writers store whole padded rows instead (whole 128-byte lines:
  * partial lines cost a read-modify-write) and so rewrite the halo rows / columns of the planes they write with +0.0, the value
- * the halo holds: the two-axis Winograd Conv2d (its finish kernel) and the fp32 s3r_cost_volume_forward.  Neither ever writes
- * anything but +0.0 there, nor a halo PLANE (depth) of a 3D output.  (The plain tensor inside an S3R_LAYOUT_DIFF output is written
+ * the halo holds: the two-axis Winograd Conv2d (its finish kernel), the semi-fused launch form of the two-axis Conv3d k3 s1 p1
+ * (its finish kernel stores whole padded depth slices) and the fp32 s3r_cost_volume_forward.  None ever writes anything but +0.0
+ * there; the first and the last never touch a halo PLANE (depth) of a 3D output, the semi-fused Conv3d form rewrites those of its
+ * output with +0.0 too.  (The plain tensor inside an S3R_LAYOUT_DIFF output is written
  * whole, every halo element with +0.0: that layout exists between two layers of a chain only.)  s3r_chain_forward plans the halos of all
  * intermediates itself and pads an unpadded chain input on the fly. */
 typedef struct s3r_conv_desc {

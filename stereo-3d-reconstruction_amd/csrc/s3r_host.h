@@ -12,6 +12,9 @@ namespace s3rh {
 
 constexpr int64_t kMaxElems = (int64_t)1 << 31;
 constexpr int64_t kMaxBytes = (int64_t)1 << 32;
+// padded output edges the two-axis Winograd finish kernels can stage in 64 KiB of LDS (include/s3r.h, s3r_algo): one fp32 plane of
+// 128^2 (Conv2d), four slices of 64^2 (the semi-fused Conv3d form, which the plan offers up to an edge of 60)
+constexpr int kWino2PlaneEdge = 128, kWino2SemiEdge = 64, kWino2SemiMaxEdge = 60;
 
 // ---------------------------------------------------------------- errors (s3r_plan.hip): thread-local message behind s3r_last_error
 const char* last_error();
@@ -125,6 +128,8 @@ Dwino3Need dwino3_need(const s3r_conv_desc* d, int form);
 bool wino_desc_ok(const s3r_conv_desc* d);
 int wino2_ax(const s3r_conv_desc* d);
 bool wino2_desc_ok(const s3r_conv_desc* d);
+bool wino2_plane_fits(const s3r_conv_desc* d);
+bool wino2_semi_fits(const s3r_conv_desc* d);
 int wino2_max_edge();
 int resolve_algo(const s3r_conv_desc* d, int* alg, int* form);
 bool resolves_to_wino(const s3r_conv_desc* d);

@@ -378,6 +378,17 @@ int wino2_ax(const s3r_conv_desc* d) {
     if (d->k == 4 && d->pad == 0 && d->in_size >= 5) return 1;
     return -1;
 }
+// The LDS rule of the two-axis finish kernels (s3r_conv_wino.hip, launch_conv_wino2: it keeps its own checks).  Both stage PADDED
+// output planes in 64 KiB: the Conv2d finish one plane, (out + 2 out_halo)^2 floats, hence a padded edge <= 128 (a layer writing
+// its consumer's plane sets stages the halo-1 plane: always inside, the edge stops at 124); the semi-fused Conv3d finish four
+// slices, hence a padded edge <= 64.  The class-parallel Conv3d form stages nothing.  Part of the PLAN: a descriptor outside the
+// rule is refused by resolve_algo (or planned in the class-parallel form), never by the launcher behind an enqueued transform
+bool wino2_plane_fits(const s3r_conv_desc* d) {
+    return wino2_ax(d) != 2 || d->out_layout == S3R_LAYOUT_WINO_HW || out_size(d) + 2 * d->out_halo <= kWino2PlaneEdge;
+}
+bool wino2_semi_fits(const s3r_conv_desc* d) {
+    return wino2_ax(d) == 2 || (wino2_ax(d) == 0 && d->in_size <= kWino2SemiMaxEdge && out_size(d) + 2 * d->out_halo <= kWino2SemiEdge);
+}
 bool wino2_desc_ok(const s3r_conv_desc* d) {
     return wino2_ax(d) >= 0 && d->act < S3R_ACT_SIGMOID && dil_of(d) == 1 && d->in_halo == d->pad && d->ksplit <= 1 &&
            (d->in_layout == S3R_LAYOUT_PLAIN || (d->in_layout == S3R_LAYOUT_WINO_DH && wino2_ax(d) == 0 && d->in_size % 4 == 0) ||
@@ -438,15 +449,22 @@ int resolve_algo(const s3r_conv_desc* d, int* alg, int* form) {
         // tile: -1 the library's pick between the forms the layer has; 0, 1, 2 a launch form of the one-axis kernel; 3 the two-axis
         // algorithm (4: its class-parallel form, 5: its semi-fused form)
         if ((d->tile >= 3 && !two) || (d->tile >= 0 && d->tile <= 2 && !one) || (!one && !two) || d->tile > 5 ||
-            (d->tile == 5 && (wino2_ax(d) == 1 || (wino2_ax(d) == 0 && d->in_size > 60))))      // (semi-fused 3D: four padded slices in LDS)
+            (d->tile == 5 && wino2_ax(d) == 1))
             return fail(S3R_ERR_INVALID, "algo = WINOGRAD: this layer / descriptor has no such Winograd form (one-axis: fp32 Conv k3 s1 p1 "
                         "with cin %% %d == 0 and edge >= 4, or ConvTranspose3d k4 s2 p1 over an edge %% 4 == 0, in_halo = 1; two-axis "
                         "(tile = 3): Conv3d k3 s1 p1 / k4 s1 p0, in_halo = pad; plain layouts, no split-K, no sigmoid)", s3r::wino_bk());
+        if (d->tile == 5 && !wino2_semi_fits(d))      // (tile 3 / -1 plan such a layer class-parallel: wino2_form_of)
+            return fail(S3R_ERR_INVALID, "algo = WINOGRAD, tile = 5: the semi-fused form of a Conv3d stages four padded output slices in 64 KiB of "
+                        "LDS: edge <= %d and edge + 2 out_halo <= %d (got %d + 2 x %d); the class-parallel form (tile = 4) has no such bound",
+                        kWino2SemiMaxEdge, kWino2SemiEdge, out_size(d), d->out_halo);
         const bool two_io = two_axis_io(d);
         if (two_io && !(two && (d->tile < 0 || d->tile >= 3)))
             return fail(S3R_ERR_INVALID, "a two-axis transformed input / output runs the two-axis kernel only");
         if (d->tile >= 3 || !one || two_io ||
-            (d->tile < 0 && two && d->in_layout == S3R_LAYOUT_PLAIN && d->in_size <= wino2_max_edge())) {
+            (d->tile < 0 && two && d->in_layout == S3R_LAYOUT_PLAIN && d->in_size <= wino2_max_edge() && wino2_plane_fits(d))) {
+            if (!wino2_plane_fits(d))
+                return fail(S3R_ERR_INVALID, "algo = WINOGRAD: the two-axis form of a Conv2d stages one padded output plane in 64 KiB of LDS: "
+                            "edge + 2 out_halo <= %d (got %d + 2 x %d)", kWino2PlaneEdge, out_size(d), d->out_halo);
             *alg = ALG_WINO2;
             *form = d->tile >= 4 ? d->tile - 4 : -1;
         } else { *alg = ALG_WINO; *form = d->tile; }
@@ -457,6 +475,9 @@ int resolve_algo(const s3r_conv_desc* d, int* alg, int* form) {
         if (d->algo == S3R_ALGO_DIRECT || !wino2_desc_ok(d) || d->tile >= 0)
             return fail(S3R_ERR_INVALID, "a two-axis transformed input / output runs the two-axis kernel only: algo AUTO / WINOGRAD, no direct "
                         "tile / split-K override");
+        if (!wino2_plane_fits(d))
+            return fail(S3R_ERR_INVALID, "the two-axis form of a Conv2d stages one padded output plane in 64 KiB of LDS: edge + 2 out_halo <= %d "
+                        "(got %d + 2 x %d)", kWino2PlaneEdge, out_size(d), d->out_halo);
         *alg = ALG_WINO2;
         return S3R_OK;
     }
@@ -478,7 +499,7 @@ int resolve_algo(const s3r_conv_desc* d, int* alg, int* form) {
         return fail(S3R_ERR_INVALID, "the general two-axis layout is read by the two-axis kernel and written by a convolution only");
     if (d->algo == S3R_ALGO_DIRECT || d->tile >= 0 || d->ksplit >= 1 || wino_mode() <= 0) return S3R_OK;
     if (d->out_layout == S3R_LAYOUT_WINO_3D) return S3R_OK;      // (a convolution without the two-axis form: its split-K finish writes the planes)
-    if (wino2_desc_ok(d) && d->in_size <= wino2_max_edge()) *alg = ALG_WINO2;
+    if (wino2_desc_ok(d) && d->in_size <= wino2_max_edge() && wino2_plane_fits(d)) *alg = ALG_WINO2;
     // transposed layers with an edge >= 16: the three-axis form (27 / 64 of the multiplications).  r05, d3 (16^3 -> 32^3, fused head)
     // inside the forward: 0.694 -> 0.622 ms at B = 32, -4 % at B = 8 / 16, equal at 4, +5 % at B = 1 / 2 (serial form only: 64
     // workgroups); at edge 8 (d2) its one round of long workgroups loses to the two-axis form's dual launch (0.438 vs 0.380 ms)
@@ -583,9 +604,9 @@ double wino_exec_flops(const s3r_conv_desc* d, const Geo& g) {
 }
 
 // the launch form of a two-axis call (0 class-parallel, 1 semi-fused): the library's plan unless forced; a 3D layer whose four padded
-// output slices do not fit the semi-fused finish kernel's LDS stays class-parallel
+// output slices do not fit the semi-fused finish kernel's LDS WITH THIS out_halo (wino2_semi_fits) stays class-parallel
 int wino2_form_of(const s3r_conv_desc* d, int ntotal, int forced) {
-    if (forced < 0 && wino2_ax(d) == 0 && d->in_size > 60) forced = 0;
+    if (forced < 0 && !wino2_semi_fits(d)) forced = 0;
     return s3r::wino2_form(wino2_ax(d), d->cout, ntotal, forced);
 }
 // scratch of a two-axis call: [V of one sub-batch (unless the producer wrote it) | slabs of the launch form planned for the batch]

@@ -62,13 +62,23 @@ def has_wino(c):
         return False
     if l.op in ("conv2d", "conv3d"):
         return l.cin % 32 == 0 and l.cout > 1 and l.dil == 1 and l.s == 1 and ((l.k, l.p) == (3, 1) or (l.op == "conv3d" and (l.k, l.p) == (4, 0)))
-    return l.op == "deconv3d" and (l.k, l.s, l.p, l.dil, l.opad) == (4, 2, 1, 1, 0) and l.cin % 32 == 0 and c.n_in % 4 == 0
+    if l.op != "deconv3d" or (l.k, l.s, l.p, l.dil, l.opad) != (4, 2, 1, 1, 0):
+        return False
+    if c.algo == WINO and c.tile in (6, 7, 8):         # the three-axis form: 16-channel K tiles, edges 8 / 16 / 32
+        return l.cin % 16 == 0 and c.n_in in (8, 16, 32)
+    return l.cin % 32 == 0 and c.n_in % 4 == 0
 
 
 def zero_halo_writer(c):
-    """the two-axis Conv2d form: its finish kernel stores whole padded planes, the halo as +0.0 (include/s3r.h, Halos)"""
+    """the two-axis Conv2d form: its finish kernel stores whole padded planes, the halo as +0.0; the FORCED semi-fused form of the
+    two-axis Conv3d k3: whole padded slices, the depth halo too (include/s3r.h, Halos).  (Where the library picks the Conv3d's launch
+    form, the cases here have batches at which it is the class-parallel one, which writes interiors only: held to that.)"""
     l = c.layer
-    if not has_wino(c) or l.op != "conv2d":
+    if not has_wino(c):
+        return False
+    if l.op == "conv3d":
+        return c.algo == WINO and c.tile == 5 and l.k == 3
+    if l.op != "conv2d":
         return False
     return c.tile in (3, 4, 5) or (c.algo == 0 and c.tile < 0 and c.n_in <= 28)
 
@@ -134,6 +144,32 @@ def _conv_cases():
         ConvCase("elu-pass-conv3d-32to32-e8", L("t", "conv3d", 32, 32, 3, 1, 1, True, "elu"), 8, 2),
         ConvCase("head-conv2d-48to1-sigmoid-e6", L("t", "conv2d", 48, 1, 1, 1, 0, False, "sigmoid"), 6, 3),
     ]
+    return cases + _wino_shape_cases()
+
+
+def _wino_shape_cases():
+    """one guarded case per branch of tests/_exact_cases.py::_wino_shapes (that table holds the reasons for each shape): random data
+    in poisoned buffers is the half that catches a READ outside the tensor, which integers in plain allocations cannot"""
+    c2 = lambda ci, co: L("t", "conv2d", ci, co, 3, 1, 1)
+    c3 = lambda ci, co: L("t", "conv3d", ci, co, 3, 1, 1)
+    k4 = L("t", "conv3d", 32, 48, 4, 1, 0)
+    forms = ("serial", "class-parallel", "dual")
+    cases = []
+    # one axis: every row at one launch form, the forms rotating; the last row under AUTO too (the one-axis kernel above edge 28)
+    for i, (l, n, B) in enumerate(((c2(32, 33), 5, 3), (c2(32, 33), 6, 3), (c2(32, 33), 7, 3), (c2(32, 48), 4, 1), (c3(32, 40), 9, 1),
+                                   (c3(96, 70), 6, 2), (c3(32, 2), 4, 1), (c2(32, 130), 41, 13), (c2(64, 2), 30, 1))):
+        cases.append(ConvCase(f"ws1-{forms[(i + 1) % 3]}-{l.op}-{l.cin}to{l.cout}-e{n}-B{B}", l, n, B, algo=WINO, tile=(i + 1) % 3, out_halo=i % 4))
+    cases.append(ConvCase("ws1-auto-conv2d-64to2-e30-B1", c2(64, 2), 30, 1, out_halo=1))
+    # two axes: ragged groups, ragged packs (B % PL, PL and SUB shrunk by LDS under out_halo 8), the largest plane / slices that fit
+    for l, n, B, tile, oh in ((c2(32, 33), 5, 3, 3, 1), (c2(32, 33), 6, 3, 4, 2), (c2(32, 33), 7, 3, 5, 3), (c2(32, 64), 28, 7, 3, 0),
+                              (c2(32, 2), 12, 23, 4, 8), (c2(32, 2), 124, 1, 5, 2),
+                              (c3(32, 40), 5, 3, 3, 1), (c3(32, 40), 6, 3, 4, 2), (c3(32, 40), 9, 2, 5, 3), (c3(32, 2), 8, 5, 5, 8),
+                              (c3(32, 2), 60, 1, 5, 2),
+                              (k4, 5, 3, 3, 0), (k4, 6, 3, 4, 1), (k4, 8, 3, 3, 2)):
+        cases.append(ConvCase(f"ws2-tile{tile}-{l.op}-k{l.k}-{l.cin}to{l.cout}-e{n}-B{B}-oh{oh}", l, n, B, algo=WINO, tile=tile, out_halo=oh))
+    # transposed: the two-axis classes at edge 12, the three-axis form at cin 16 / cout 40
+    cases.append(ConvCase("wsd-class-parallel-deconv3d-32to24-e12-B1", L("t", "deconv3d", 32, 24, 4, 2, 1), 12, 1, algo=WINO, tile=1, out_halo=1))
+    cases.append(ConvCase("ws3-tile6-deconv3d-16to40-e8-B3", L("t", "deconv3d", 16, 40, 4, 2, 1), 8, 3, algo=WINO, tile=6, out_halo=2))
     return cases
 
 

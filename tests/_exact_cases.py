@@ -60,6 +60,7 @@ class XCase:
     out_halo: int = 0
     refused: bool = False      # the library refuses this configuration: asserted refused, never launched
     twice: bool = False        # also run over zero-filled scratch (descriptors tests/test_buffers_gpu.py does not run)
+    ran: tuple = ()            # the profiler record's `ran` must be one of these (s3r._lib.RAN); (): not asserted
 
     layer = property(lambda self: self.data.layer)
     n_in = property(lambda self: self.data.n_in)
@@ -258,6 +259,106 @@ def _wino():
 
 WINO_CASES = _wino()
 
+# ---------------------------------------------------------------- Winograd fp32 at ragged shapes and at the LDS limits
+ONE_AXIS_RAN = ("winograd-serial", "winograd-class-parallel", "winograd-dual")
+DUAL_CASE = "ws1-dual-conv2d-32to130-e41-B13"      # asserted to have run the dual form: 276 serial workgroups on 256 compute units
+
+
+def serial_workgroups(l, n_in, B):
+    """workgroups of the one-axis kernel's serial form (tests/test_wino_gpu.py::_positions): 64-cout x 64-position tiles"""
+    n = B * (n_in if l.op == "conv3d" else 1) * -(-n_in // 4) * n_in
+    return -(-l.cout // 64) * -(-n // 64)
+
+
+def _wino_shapes():
+    """The smallest shapes at which each branch of the Winograd kernels is taken that the network's own sizes never reach: edges
+    with n mod 4 = 1, 2, 3 (the dword-gather instantiation of the one-axis kernel, ragged last groups along one or both axes), couts
+    2 / 33 / 70 / 130 over position counts that end inside a 64-position tile, ragged last packs of the two finish kernels (B % PL,
+    PL and SUB shrunk by LDS under out_halo = 8), and the largest padded planes / slices that fit 64 KiB of LDS.  Every launch form
+    of an algorithm is a case of its own over ONE Data; out_halo cycles through 0 .. 3 over the rows that fix none."""
+    cases = []
+    seed = 850
+    names = {0: "serial", 1: "class-parallel", 2: "dual"}
+    c2 = lambda ci, co: L("t", "conv2d", ci, co, 3, 1, 1)
+    c3 = lambda ci, co: L("t", "conv3d", ci, co, 3, 1, 1)
+    row = [0]
+
+    def halo():
+        row[0] += 1
+        return (row[0] - 1) % 4
+
+    # one axis, F(4, 3) along H: 0 serial, 1 class-parallel, 2 dual.  B = 13 at edge 41: 13 x 11 x 41 positions in 92 tiles x 3
+    # cout tiles = 276 serial workgroups, past the 256 compute units — what the dual form needs to cut inside the layer
+    for l, n, B in ((c2(32, 33), 5, 3), (c2(32, 33), 6, 3), (c2(32, 33), 7, 3), (c2(32, 48), 4, 1), (c3(32, 40), 9, 1), (c3(96, 70), 6, 2),
+                    (c3(32, 2), 4, 1), (c2(32, 130), 41, 13), (c2(64, 2), 30, 1)):
+        d, oh = _wino_data(l, B, n, seed, "f43-h"), halo()
+        tag = f"{l.op}-{l.cin}to{l.cout}-e{n}-B{B}"
+        for t in (0, 1, 2):
+            cid = f"ws1-{names[t]}-{tag}"
+            ran = (ONE_AXIS_RAN[t],) if t < 2 or cid == DUAL_CASE else ONE_AXIS_RAN      # (dual falls back where no cut exists)
+            cases.append(XCase(cid, d, tile=t, algo=WINO, out_halo=oh, twice=True, ran=ran))
+        if n > 28:                                     # AUTO takes the one-axis kernel above the two-axis form's edge 28
+            cases.append(XCase(f"ws1-auto-{tag}", d, out_halo=oh, twice=True, ran=ONE_AXIS_RAN))
+    assert serial_workgroups(c2(32, 130), 41, 13) == 276
+    # two axes, F(4, 3) x F(4, 3): 3 the library's launch form, 4 class-parallel, 5 semi-fused; AUTO up to edge 28
+    two = [(c2(32, 33), n, 3, None) for n in (4, 5, 6, 7, 9, 10, 11)]
+    two += [(c2(32, 64), 28, 7, None),                 # 49 groups per sample: PL = 5 samples per finish workgroup, packs of 5 + 2
+            (c2(32, 2), 12, 23, 8),                    # 9 groups: PL = 23 by the batch, 20 by LDS (28^2 floats a plane), packs of 20 + 3
+            (c2(64, 130), 29, 2, None), (c2(64, 130), 30, 1, None)]
+    two += [(c3(32, 40), n, B, None) for n, B in ((4, 3), (5, 3), (6, 3), (9, 2), (10, 2), (11, 1))]
+    two += [(c3(96, 70), 6, 2, None),
+            (c3(32, 2), 8, 5, 8)]                      # SUB = 10 (sample, depth group) pairs, 7 by LDS (four 24^2 slices each): items of 7 + 3
+    for l, n, B, oh in two:
+        d, oh = _wino_data(l, B, n, seed, "f43x2"), halo() if oh is None else oh
+        tag = f"{l.op}-{l.cin}to{l.cout}-e{n}-B{B}-oh{oh}"
+        for t in (3, 4, 5) + ((0,) if n <= 28 else ()):
+            if t:
+                cases.append(XCase(f"ws2-tile{t}-{tag}", d, tile=t, algo=WINO, out_halo=oh, twice=True, ran=("winograd-2axis",)))
+            else:
+                cases.append(XCase(f"ws2-auto-{tag}", d, out_halo=oh, twice=True, ran=("winograd-2axis",)))
+    # the limits (include/s3r.h, s3r_algo): a padded plane of 128^2 floats, four padded slices of 64^2, are exactly 64 KiB
+    d = _wino_data(c2(32, 2), 1, 124, seed, "f43x2")
+    for oh in (0, 2):
+        for t in (3, 4, 5):
+            cases.append(XCase(f"ws2-tile{t}-conv2d-32to2-e124-B1-oh{oh}", d, tile=t, algo=WINO, out_halo=oh, twice=True, ran=("winograd-2axis",)))
+    d = _wino_data(c3(32, 2), 1, 60, seed, "f43x2")
+    for oh in (0, 2):
+        for t in (4, 5):
+            cases.append(XCase(f"ws2-tile{t}-conv3d-32to2-e60-B1-oh{oh}", d, tile=t, algo=WINO, out_halo=oh, twice=True, ran=("winograd-2axis",)))
+    # F(2, 4) x F(2, 4): output edges 2, 3, 5, 6 (v6 has 4); no semi-fused form
+    for l, n, B in ((L("t", "conv3d", 32, 48, 4, 1, 0), 5, 3), (L("t", "conv3d", 32, 48, 4, 1, 0), 6, 3), (L("t", "conv3d", 32, 48, 4, 1, 0), 8, 3),
+                    (L("t", "conv3d", 64, 20, 4, 1, 0), 9, 2)):
+        d, oh = _wino_data(l, B, n, seed, "f24x2"), halo()
+        tag = f"conv3d-k4-{l.cin}to{l.cout}-e{n}-B{B}-oh{oh}"
+        for t in (3, 4):
+            cases.append(XCase(f"ws2-tile{t}-{tag}", d, tile=t, algo=WINO, out_halo=oh, twice=True, ran=("winograd-2axis",)))
+        cases.append(XCase(f"ws2-auto-{tag}", d, out_halo=oh, twice=True, ran=("winograd-2axis",)))
+    # transposed: F(2, 2) along D and H (the library's pick and the three launch forms), and the three-axis form
+    for l, n, B in ((L("t", "deconv3d", 32, 24, 4, 2, 1), 4, 3), (L("t", "deconv3d", 32, 24, 4, 2, 1), 12, 1), (L("t", "deconv3d", 64, 72, 4, 2, 1), 8, 1)):
+        d, oh = Data(l, B, n, seed, "f22x2"), halo()
+        for t in (-1, 0, 1, 2):
+            cases.append(XCase(f"wsd-tile{t}-deconv3d-{l.cin}to{l.cout}-e{n}-B{B}-oh{oh}", d, tile=t, algo=WINO, out_halo=oh, twice=True,
+                               ran=(ONE_AXIS_RAN[t],) if t in (0, 1) else ONE_AXIS_RAN))
+    for l, n, B in ((L("t", "deconv3d", 16, 40, 4, 2, 1), 8, 3), (L("t", "deconv3d", 48, 24, 4, 2, 1), 16, 1)):
+        d, oh = Data(l, B, n, seed, "f22x3"), halo()
+        for t in (6, 7, 8):
+            cases.append(XCase(f"ws3-tile{t}-deconv3d-{l.cin}to{l.cout}-e{n}-B{B}-oh{oh}", d, tile=t, algo=WINO, out_halo=oh, twice=True,
+                               ran=("winograd-3axis", "winograd-3axis-class-parallel")))
+    return cases
+
+
+WINO_SHAPE_CASES = _wino_shapes()
+
+
+def auto_form(c):
+    """the Winograd form include/s3r.h's policy resolves an AUTO convolution of the sweep to: the two-axis algorithm for every stride-1
+    layer that has it and an edge <= 28, the one-axis kernel above"""
+    l = c.layer
+    if (l.k, l.p) == (4, 0):
+        return "f24x2"
+    return "f43x2" if c.n_in <= 28 else "f43-h"
+
+
 # ---------------------------------------------------------------- producers that hand a consumer its input: cost volume, chains
 @dataclass(frozen=True)
 class CVCase:
@@ -328,7 +429,7 @@ def _chains():
 
 CHAIN_CASES = _chains()
 
-ALL_CASES = DIRECT_CASES + LINEAR_CASES + BF16_CASES + WINO_CASES
+ALL_CASES = DIRECT_CASES + LINEAR_CASES + BF16_CASES + WINO_CASES + WINO_SHAPE_CASES
 
 
 def unique_data(cases=None):

@@ -179,7 +179,8 @@ def _within_np(got, ref, bnd, what):
 
 
 # ---------------------------------------------------------------- s3r_conv_pack_weights + s3r_conv_forward
-def _conv(cc):
+def _conv(cc, refused_out_halo=None):
+    """refused_out_halo: the forward with this out_halo in the descriptor is refused with S3R_ERR_INVALID (the plan's `refuse`)"""
     l, nd, bf, B = cc.layer, R.ndim(cc.layer), cc.dtype == "bf16", cc.B
     stem, head = BC._stem(l), BC._head(l, cc.n_in)
     cl_in, cl_out = bf and not stem, bf and not head
@@ -229,7 +230,14 @@ def _conv(cc):
             ref, mag = R.ref64(l, x, p)
             _within(got.float(), ref, R.bound(l, ref, mag, cc.form), cc.id)
 
-        return Plan(args, data, call, check, keep=desc)
+        refuse = None
+        if refused_out_halo is not None:               # (the forward alone: a refused call reads no packed weights)
+            bad = s3r._lib.make_desc(l, B, cc.n_in, tile=cc.tile, in_halo=ih, out_halo=refused_out_halo, ksplit=cc.ksplit,
+                                     dtype=s3r._lib.DTYPE[cc.dtype], algo=cc.algo)
+            assert lib.s3r_conv_scratch_elems(C.byref(bad)) == -1, "expected to be refused"
+            refuse = lambda ptr, st: (lib.s3r_conv_forward(C.byref(bad), ptr["x"], ptr["packed"], ptr.get("scale"), ptr["shift"], ptr["y"],
+                                                           ptr["scratch"], need, st), -1)
+        return Plan(args, data, call, check, refuse=refuse, keep=desc)
 
     return make
 
@@ -766,6 +774,11 @@ def _disparity_metrics(lib, dev):
 # ---------------------------------------------------------------- the table
 _CONV_E = ("s3r_conv_pack_weights", "s3r_conv_forward")
 CASES = [Case(f"conv:{c.id}", _CONV_E, "conv", _conv(c), mutant=c.id.startswith("splitk2")) for c in CONV]
+# the two-axis Conv2d at its largest edge; with out_halo 3 its padded plane (130^2 floats) passes the finish kernel's 64 KiB of LDS:
+# refused when the algorithm is resolved (include/s3r.h, s3r_algo) — the launcher used to refuse it behind an enqueued input transform
+CONV_AT_THE_LDS_LIMIT = "conv:wino2-conv2d-32to2-e124"
+CASES.append(Case(CONV_AT_THE_LDS_LIMIT, _CONV_E, "conv",
+                  _conv(_CC("wino2-conv2d-32to2-e124", L("t", "conv2d", 32, 2, 3, 1, 1), 124, 1, algo=W, tile=3), refused_out_halo=3)))
 CASES += [Case(f"chain:{n}", ("s3r_chain_forward",), "chain", _chain(n, parts), mutant=n.startswith("handoff")) for n, parts in CHAINS.items()]
 CASES += [
     Case("encoder:fp32", ("s3r_encoder_forward",), "stage", _encoder("fp32", False)),
@@ -805,3 +818,4 @@ INSTRUMENTS = {"delayed_producer": CASES, "capture_replay": CASES}
 MUTANTS = [c for c in CASES if c.mutant]
 REFUSALS = [c for c in CASES if c.entries[0] in TRAINING and c.id in (
     "linear_backward:3x96x40-sigmoid", "chamfer_backward", "voxel_bce_forward", "voxel_bce_backward", "head_backward:all")]
+REFUSALS.append(BY_ID[CONV_AT_THE_LDS_LIMIT])

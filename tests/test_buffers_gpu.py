@@ -8,6 +8,8 @@ bound.  The cost volume, Chamfer, IoU and winner-take-all read-out stay bit-exac
 Largest |got - ref| / bound measured on an MI355X, per family (the seeds are fixed and every kernel is deterministic): direct fp32
 0.30 (staged-conv3d-5to7-k1-e6: K = 5, where a few ulp are a third of the bound), Winograd 0.055 (v1-fp32-B3-oh3), bf16 0.43
 (v5-bf16-B1-oh1, tests/test_bf16_gpu.py's tolerance), chains 0.035 (unfolded->unfolded-c1).  The file runs in about 10 s.
+The 26 Winograd cases at ragged shapes and LDS limits (tests/_buffer_cases.py::_wino_shape_cases) stay below 0.042
+(ws2-tile5-conv3d-k3-32to2-e60-B1-oh2) and add 0.1 s.
 
 The call bodies live in tests/_abi_bodies.py: tests/test_alignment_gpu.py runs the same bodies with every payload moved off its
 256-byte boundary.

@@ -40,6 +40,26 @@ def test_case_is_admissible(d):
     assert LT.admissible(rec, d.bf16_out) is None, (LT.admissible(rec, d.bf16_out), rec)
 
 
+AUTO_SWEEP = [c for c in X.WINO_SHAPE_CASES if c.algo == 0]
+
+
+@pytest.mark.parametrize("c", AUTO_SWEEP, ids=[c.id for c in AUTO_SWEEP])
+def test_auto_case_is_admissible_under_the_form_it_resolves_to(s3r, lib, c):
+    """a sweep case under algo = AUTO runs whatever the policy picks: its data must be on THAT form's lattice with that form's flow
+    below 2^24 (two-axis data is one-axis data too — multiples of 576 are multiples of 24, one tap per joint fibre is at most one per
+    H fibre — but not the other way round, and the flow differs), and the planner must resolve it to a Winograd form at all"""
+    form = X.auto_form(c)
+    x, p = c.data.make()
+    rec = LT.exactness(c.layer, x, p, form)
+    assert LT.admissible(rec) is None, (form, LT.admissible(rec), rec)
+    assert c.data.form == form or (c.data.form, form) == ("f43x2", "f43-h"), (c.data.form, form)
+    # (host only: AUTO plans a transformed input for this descriptor exactly when it resolves to a Winograd form over an edge % 4 == 0;
+    # at other edges the scratch of the forced algorithm is what AUTO asks for too)
+    auto, forced = _desc(s3r, c), _desc(s3r, dataclasses.replace(c, algo=X.WINO, tile=3 if form != "f43-h" else -1))
+    need = lib.s3r_conv_scratch_elems(C.byref(auto))
+    assert need > 0 and need == lib.s3r_conv_scratch_elems(C.byref(forced)), (need, lib.s3r_last_error())
+
+
 # ---------------------------------------------------------------- mutation self-test
 def _one_channel(layer, p, o):
     w = p["w"]
@@ -166,6 +186,51 @@ def _desc(s3r, c):
 
 
 CONV = [c for c in X.ALL_CASES if c.layer.op != "linear" and c.dtype == "fp32"]
+
+
+def _plans(s3r, lib, l, n, tile, oh):
+    d = s3r._lib.make_desc(l, 1, n, tile=tile, in_halo=1, out_halo=oh, algo=X.WINO)
+    r = lib.s3r_conv_scratch_elems(C.byref(d))
+    return r >= 0, r, lib.s3r_last_error()
+
+
+def test_two_axis_lds_rule_is_the_planners(s3r, lib):
+    """include/s3r.h, s3r_algo: the two-axis Conv2d form (tile 3, 4, 5) serves an edge n <= 124 with n + 2 out_halo <= 128, the
+    semi-fused Conv3d form (tile 5) n <= 60 with n + 2 out_halo <= 64; the class-parallel Conv3d form (tile 4) has no such bound and
+    the library's pick (tile 3) takes it outside the semi-fused form's.  The scratch query plans a descriptor if and only if that
+    rule holds — restated here from the header, not from the planner: before this test the planner knew the edge bounds only, and
+    the launcher refused the rest behind an enqueued input transform (177 of the 756 descriptors here disagreed)."""
+    wrong = []
+    for n in range(112, 126):
+        for oh in range(9):
+            for tile in (3, 4, 5):
+                ok, r, msg = _plans(s3r, lib, X.L("t", "conv2d", 32, 2, 3, 1, 1), n, tile, oh)
+                want = n <= 124 and n + 2 * oh <= 128
+                if ok != want or (not ok and n <= 124 and b"128" not in msg):
+                    wrong.append(("conv2d", n, oh, tile, want, r, msg))
+    for n in range(48, 62):
+        for oh in range(9):
+            for tile in (3, 4, 5):
+                ok, r, msg = _plans(s3r, lib, X.L("t", "conv3d", 32, 2, 3, 1, 1), n, tile, oh)
+                want = tile != 5 or (n <= 60 and n + 2 * oh <= 64)
+                if ok != want or (not ok and b"64" not in msg):
+                    wrong.append(("conv3d", n, oh, tile, want, r, msg))
+    assert not wrong, (len(wrong), wrong[:8])
+
+
+def test_library_pick_sizes_its_scratch_for_the_form_it_can_launch(s3r, lib):
+    """Conv3d 32 -> 2 over edge 60 with out_halo 3 under algo = WINOGRAD, tile = 3 (the two-axis algorithm in the library's launch
+    form) at batches where the library would take the semi-fused form: four 66^2 slices do not fit, so the plan is the
+    class-parallel form's — for ANY batch the scratch is that of tile 4.  (tile = -1 resolves this edge, above 28, to the one-axis
+    kernel, which has no such bound.)"""
+    l = X.L("t", "conv3d", 32, 2, 3, 1, 1)
+    for B in (1, 2, 8):
+        need = {}
+        for tile in (-1, 3, 4):
+            d = s3r._lib.make_desc(l, B, 60, tile=tile, in_halo=1, out_halo=3, algo=X.WINO)
+            need[tile] = lib.s3r_conv_scratch_elems(C.byref(d))
+        one = s3r._lib.make_desc(l, B, 60, tile=1, in_halo=1, out_halo=3, algo=X.WINO)      # (the library's pick is sized class-parallel)
+        assert need[3] == need[4] > 0 and need[-1] == lib.s3r_conv_scratch_elems(C.byref(one)) > 0, (B, need, lib.s3r_last_error())
 
 
 def test_refusals_match_the_planner(s3r, lib):

@@ -23,9 +23,17 @@ difference in lattice units (2^-f): a difference equal to one `w x` product name
 Cases: direct fp32 233 (18 network layers x B 1 / 3, 8 shapes x 8 tiles x 2 gather widths, split-K 1 / 2 / 4 and v5 / v6 / d1 at
 network size under split-K 1 .. 16, the general-layer families), linear 28, bf16 260 under each of the two matrix instructions
 (18 layers x B 1 / 3, the 14 x 16 tile matrix), Winograd 48 (one-axis x 3 launch forms, two-axis tiles 3 / 4 / 5 incl. F(2,4) x F(2,4),
-transposed F(2,2) classes and the three-axis form), the cost volume writing v1's plane sets in both layouts, the stem -> e2 hand-off,
-the bf16 d3 + head fused launch, and four runs that drop ONE term on the device and require the mismatch.  On an MI355X every one
-of them is bit-exact: the tests found no kernel or pack bug.
+transposed F(2,2) classes and the three-axis form), Winograd at ragged shapes and at the LDS limits 143 (tests/_exact_cases.py::
+_wino_shapes: the smallest shapes at which each branch of those kernels is taken — edges with n mod 4 = 1, 2, 3 and the dword-gather
+instantiation of the one-axis kernel, F(2,4) x F(2,4) at output edges 2, 3, 5, 6, couts 2 / 33 / 70 / 130, ragged last packs of the
+two finish kernels, PL and SUB shrunk by LDS under out_halo 8, a padded plane of 128^2 and four padded slices of 64^2 floats; every
+launch form and AUTO, the profiler record naming the form that ran), the cost volume writing v1's plane sets in both layouts, the
+stem -> e2 hand-off, the bf16 d3 + head fused launch, and four runs that drop ONE term on the device and require the mismatch.  On
+an MI355X every one of them is bit-exact: the tests found no kernel or pack bug.
+
+Past the LDS limits (a padded plane of 130^2, four slices of 66^2) the descriptor is refused by the scratch query and by the forward,
+with the NaN fill of the output and the scratch intact, and the library's own launch form at such a shape is the class-parallel one:
+three tests beside the sweep (the planner half is tests/test_exact_cpu.py::test_two_axis_lds_rule_is_the_planners).
 
 Staying on tests/_ref64.py's bound (tests/test_buffers_gpu.py's chain matrix): the e6 -> e7 two-axis hand-off AS A CHAIN.  The
 producer's weights must be multiples of 576 (wax_g in s3r_conv_wino.hip folds 1/24 per axis into them), so the intermediate is
@@ -33,7 +41,10 @@ a multiple of 576, and the consumer's weights bring another 576: one unit produc
 dozen terms, whatever the data.  e6 and e7 are held exactly one at a time (wino2-tile3/4/5-e6, -e7).  The activations Sigmoid, ELU
 and Tanh stay there too (transcendental), and the 8-bit stem entry (it scales by 1/255; it is tied to the fp32 entry bit for bit).
 
-Wall time on an MI355X: `pytest tests -m gpu` without this file 144 s (1181 tests); this file 6 s (838 tests).
+Wall time on an MI355X: `pytest tests -m gpu` without this file 144 s (1181 tests); this file 6 s (838 tests).  With the shape
+sweep: 8.5 s (984 tests) — summed per-test times of one run, the 838 earlier tests 4.1 s, the 146 new ones 2.1 s, of which the
+library-pick case at edge 60 (B = 2, its fp64 reference included) 1.8 s and the first edge-124 case 0.6 s (it makes the data);
+every other new case is below 0.12 s.
 """
 import ctypes as C
 
@@ -124,17 +135,26 @@ def run_conv(s3r, lib, c):
     sc = None if p["scale"] is None else p["scale"].contiguous()
     sh = p["shift"].contiguous()
     outs = []
-    for fill in (("nan", "zero") if c.twice else ("nan",)):
-        y = torch.full(yshape, float("nan"), dtype=torch.bfloat16 if cl_out else torch.float32, device=DEV)
-        scr = torch.full((max(need, 1),), float("nan") if fill == "nan" else 0.0, device=DEV)
-        rc = lib.s3r_conv_forward(C.byref(desc), xp.data_ptr(), pk.data_ptr(), sc.data_ptr() if sc is not None else None,
-                                  sh.data_ptr(), y.data_ptr(), scr.data_ptr(), need, None)
-        sync()
-        if c.refused:                                 # bf16: the forced tile is refused when the launch is resolved, before any kernel
-            assert rc < 0 and lib.s3r_last_error() and bool(torch.isnan(y).all()), (c.id, "expected to be refused", rc)
-            return None
-        rc_ok(lib, rc, c.id)
-        outs.append(interior(y, oh, sp, cl_out).contiguous())
+    if c.ran:
+        s3r.profile_enable(8)
+    try:
+        for fill in (("nan", "zero") if c.twice else ("nan",)):
+            y = torch.full(yshape, float("nan"), dtype=torch.bfloat16 if cl_out else torch.float32, device=DEV)
+            scr = torch.full((max(need, 1),), float("nan") if fill == "nan" else 0.0, device=DEV)
+            rc = lib.s3r_conv_forward(C.byref(desc), xp.data_ptr(), pk.data_ptr(), sc.data_ptr() if sc is not None else None,
+                                      sh.data_ptr(), y.data_ptr(), scr.data_ptr(), need, None)
+            sync()
+            if c.refused:                             # bf16: the forced tile is refused when the launch is resolved, before any kernel
+                assert rc < 0 and lib.s3r_last_error() and bool(torch.isnan(y).all()), (c.id, "expected to be refused", rc)
+                return None
+            rc_ok(lib, rc, c.id)
+            outs.append(interior(y, oh, sp, cl_out).contiguous())
+        rec = [r for r in s3r.profile_read(8) if r["family"] == "conv_mfma"] if c.ran else []
+    finally:
+        if c.ran:
+            s3r.profile_enable(0)
+    if c.ran:                                         # the algorithm and launch form under test are the ones that ran
+        assert len(rec) == len(outs) and all(r["ran"] in c.ran for r in rec), (c.id, c.ran, rec)
     if len(outs) == 2:
         view = torch.int16 if cl_out else torch.int32
         assert torch.equal(outs[0].view(view), outs[1].view(view)), "the result depends on the scratch contents"
@@ -186,6 +206,77 @@ def test_bf16(s3r, lib, case, mfma_shape):
 @pytest.mark.parametrize("case", X.WINO_CASES, ids=[c.id for c in X.WINO_CASES])
 def test_winograd_fp32(s3r, lib, case):
     _check_conv(s3r, lib, case)
+
+
+@pytest.mark.parametrize("case", X.WINO_SHAPE_CASES, ids=[c.id for c in X.WINO_SHAPE_CASES])
+def test_winograd_shapes(s3r, lib, case):
+    """tests/_exact_cases.py::_wino_shapes: ragged edges, couts and packs, and the LDS limits; the profiler record names the form
+    that ran — for the dual case unconditionally (276 serial workgroups: more than this device's compute units, or B must grow)"""
+    if case.id == X.DUAL_CASE:
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        assert X.serial_workgroups(case.layer, case.n_in, case.B) > cus, ("raise B of the dual case: this device has", cus, "compute units")
+        assert case.ran == ("winograd-dual",)
+    _check_conv(s3r, lib, case)
+
+
+def _semi_fused_batch(l, n):
+    """smallest batch at which the library takes the semi-fused form of a two-axis Conv3d on this device (s3r_conv_wino.hip,
+    wino2_form: six workgroups per 64-cout x 64-position tile fill the compute units' four slots twice over)"""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    B = 1
+    while -(-l.cout // 64) * -(-(B * (-(-n // 4)) ** 2 * n) // 64) * 6 < 8 * cus:
+        B += 1
+    return B
+
+
+ERR_INVALID = -1          # S3R_ERR_INVALID (include/s3r.h)
+REFUSED_AT_THE_LIMIT = [("conv2d", 124, 3, 3, b"128"), ("conv3d", 60, 3, 5, b"64")]
+
+
+@pytest.mark.parametrize("op,n,oh,tile,bound", REFUSED_AT_THE_LIMIT, ids=[f"{r[0]}-e{r[1]}-oh{r[2]}-tile{r[3]}" for r in REFUSED_AT_THE_LIMIT])
+def test_past_the_lds_limit_is_refused_before_anything_is_enqueued(s3r, lib, op, n, oh, tile, bound):
+    """one padded plane of 130^2 floats, four padded slices of 66^2: refused by the scratch query AND by the forward — called with
+    the scratch the planner used to grant such a descriptor (what the same descriptor needs at out_halo = 2, where it fits: the
+    scratch of these forms does not depend on the output's halo) — with S3R_ERR_INVALID, a message that names the bound, and the
+    output and the scratch still holding their NaN fill.  (The forward used to enqueue the input transform and fail in the launcher.)"""
+    l = X.L("t", op, 32, 2, 3, 1, 1)
+    nd = 2 if op == "conv2d" else 3
+    desc = s3r._lib.make_desc(l, 1, n, tile=tile, in_halo=1, out_halo=oh, algo=X.WINO)
+    assert lib.s3r_conv_scratch_elems(C.byref(desc)) == ERR_INVALID and bound in lib.s3r_last_error(), lib.s3r_last_error()
+    fits = s3r._lib.make_desc(l, 1, n, tile=tile, in_halo=1, out_halo=2, algo=X.WINO)
+    need = lib.s3r_conv_scratch_elems(C.byref(fits))
+    assert need > 0, lib.s3r_last_error()
+    npk = C.c_int64(0)
+    rc_ok(lib, lib.s3r_conv_packed_elems(C.byref(fits), C.byref(npk)), "packed_elems")      # (the packed layout knows no halo)
+    g = torch.Generator().manual_seed(n)
+    w = torch.randn((2, 32) + (3,) * nd, generator=g).to(DEV)
+    pk = torch.zeros(npk.value, device=DEV)
+    rc_ok(lib, lib.s3r_conv_pack_weights(C.byref(fits), w.data_ptr(), pk.data_ptr(), None), "pack_weights")
+    x = torch.randn((1, 32) + (n + 2,) * nd, generator=g).to(DEV)
+    sc, sh = torch.ones(2, device=DEV), torch.zeros(2, device=DEV)
+    y = torch.full((1, 2) + (n + 2 * oh,) * nd, float("nan"), device=DEV)
+    scr = torch.full((need,), float("nan"), device=DEV)
+    rc = lib.s3r_conv_forward(C.byref(desc), x.data_ptr(), pk.data_ptr(), sc.data_ptr(), sh.data_ptr(), y.data_ptr(), scr.data_ptr(), need, None)
+    err = lib.s3r_last_error()
+    sync()
+    assert rc == ERR_INVALID and bound in err, (rc, err)
+    assert bool(torch.isnan(y).all()) and bool(torch.isnan(scr).all()), "a refused call wrote to its output or its scratch"
+
+
+def test_library_pick_past_the_semi_fused_limit_runs_class_parallel(s3r, lib):
+    """Conv3d 32 -> 2 over edge 60 with out_halo 3 under the two-axis algorithm in the LIBRARY's launch form (algo = WINOGRAD,
+    tile = 3), at the smallest batch at which the library takes the semi-fused form on this device: four 66^2 slices do not fit
+    its finish kernel, so the plan is the class-parallel form — the call used to fail in the launcher with an opaque HIP error.
+    That the semi-fused form did not run follows from the launcher's own check, which the refusal test above shows intact at
+    this very shape.  Bit-exact like every other form.  (tile = -1 resolves an edge above 28 to the one-axis kernel.)"""
+    l = X.L("t", "conv3d", 32, 2, 3, 1, 1)
+    B = _semi_fused_batch(l, 60)
+    assert B >= 2 and B <= 4, ("the semi-fused form from batch", B)
+    c = X.XCase("ws2-library-form-conv3d-32to2-e60-oh3", X._wino_data(l, B, 60, 850, "f43x2"), tile=3, algo=X.WINO, out_halo=3,
+                ran=("winograd-2axis",))
+    x, p = c.data.make()
+    assert LT.admissible(LT.exactness(l, x, p, "f43x2")) is None
+    _check_conv(s3r, lib, c)
 
 
 # ---------------------------------------------------------------- producers that write a consumer's input

@@ -44,7 +44,8 @@ def test_every_stream_taking_entry_is_under_both_instruments(protos, instrument)
 
 
 def test_every_training_entry_has_a_refused_call(plans):
-    assert {c.entries[0] for c in SC.REFUSALS} == set(SC.TRAINING)
+    assert {c.entries[0] for c in SC.REFUSALS if c.id != SC.CONV_AT_THE_LDS_LIMIT} == set(SC.TRAINING)
+    assert SC.BY_ID[SC.CONV_AT_THE_LDS_LIMIT] in SC.REFUSALS          # ... and the forward's refusal past the two-axis form's LDS limit
     for c in SC.REFUSALS:
         assert plans[c.id].refuse is not None, c.id
     # a refused call that leaves its outputs untouched needs outputs to look at
