@@ -1,6 +1,6 @@
 """s3r_conv_backward / s3r_conv_adjoint_desc without a GPU: the mathematics the design rests on (the weight-gradient formula and the two
-adjoint identities against torch's own float64 autograd), the mutants the cases must tell apart, the declarations and their bindings,
-and the host-side half of the entry points (the adjoint descriptor's fields, the scratch query, every refusal — each happens before
+adjoint identities against torch's own float64 autograd), the mutants the cases must tell apart, the tiling restatement (geo(), pinned
+against the library's scratch query) and the branches the sweep SHAPES reaches, the declarations and their bindings, and the host-side half of the entry points (the adjoint descriptor's fields, the scratch query, every refusal — each happens before
 anything is launched: a HIP call would have given S3R_ERR_HIP on a host without a device)."""
 import ctypes as C
 import os
@@ -16,6 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, WORKSPACE = -1, -3
 ALL = R.CASES + R.D3[:1] + R.LONG_ROWS
 RUNS = [(i, c, a) for i, c in enumerate(R.CASES) for a in R.acts_of(i)] + [(-1, c, a) for c in (R.D3[0], R.LONG_ROWS[0]) for a in ("none", "relu")]
+RUNS += [(20 + i, c, a) for i, c in enumerate(R.SHAPES) for a in ("none", "relu")]
+OLD12 = R.CASES + R.D3 + R.LONG_ROWS
 
 
 @pytest.fixture(scope="module")
@@ -82,6 +84,119 @@ def test_cases_cover_the_paths():
     assert 512 in S and any(512 < s < 1024 and s % 512 for s in S)      # a whole chunk, and a chunk boundary with a tail
     assert any(c.cin % 32 and c.cout % 32 for c in cs) and any(c.k == c.s for c in cs)
     assert R.out_edge(R.D3[0]) == 32 and R.LONG_ROWS[0].n > 64
+
+
+# ---------------------------------------------------------------- the tiling sweep
+@pytest.mark.parametrize("c", OLD12 + R.SHAPES, ids=R.case_id)
+def test_geo_restatement_is_pinned_by_the_scratch_query(s3r, lib, c):
+    """s3r_conv_backward_scratch_elems = B cout S + cout B ceil(S / 512) + (B nsl > 1 ? B nsl Ca Cf k^nd : 0) with geo()'s nsl (the host
+    library plans without a device); at B = 2 as well where the case has B = 1, so that nsl always shows.  The staged tiles fit the LDS."""
+    g = R.geo(c)
+    assert g is not None and g.lds_bytes <= 65536 and g.run in (64, 32) and g.WLP % 2 == 0 and g.WL <= g.WLP <= g.run
+    S, Ca, Cf = R.out_edge(c) ** c.nd, *((c.cin, c.cout) if c.op == "deconv" else (c.cout, c.cin))
+    for B in sorted({c.B, 2}):
+        want = B * c.cout * S + c.cout * B * ((S + 511) // 512) + (B * g.nsl * Ca * Cf * c.k ** c.nd if B * g.nsl > 1 else 0)
+        got = lib.s3r_conv_backward_scratch_elems(C.byref(desc_of(s3r, c, "relu", batch=B)))
+        assert got == want == R.scratch_elems(c, B), (B, got, want, vars(g))
+
+
+_mc = lambda c: c.n if c.op == "deconv" else R.out_edge(c)
+_Ca = lambda c: c.cin if c.op == "deconv" else c.cout
+BRANCHES = {                                              # branch of convbwd_geo / convbwd_gw_kernel / convbwd_shift_finish_kernel -> (case, geo) hits it
+    "a partial second tap group along W": lambda c, g: g.ntg == 2 and c.k % 4 != 0,
+    "a second 128-row group with inactive waves": lambda c, g: g.nag >= 2 and _Ca(c) % 128 != 0,
+    "run halved, whole rows": lambda c, g: g.run == 32 and g.nseg == 1,
+    "run halved, segments": lambda c, g: g.run == 32 and g.nseg > 1,
+    "a ragged last K slice": lambda c, g: g.nchunks % g.cps != 0,
+    "segments of a strided Conv": lambda c, g: g.nseg > 1 and c.s > 1 and c.op == "conv",
+    "segments of a strided ConvTranspose": lambda c, g: g.nseg > 1 and c.s > 1 and c.op == "deconv",
+    "segments in 3D": lambda c, g: g.nseg > 1 and c.nd == 3,
+    "mc = 64, the last whole-row shape": lambda c, g: g.mc == 64 and g.nseg == 1,
+    "mc = 65, a second segment of one position": lambda c, g: g.mc == 65 and g.nseg == 2 and g.mc - g.WL == 1,
+    "stride 3": lambda c, g: c.s == 3,
+    "k < stride": lambda c, g: c.k < c.s,
+    "coarse edge 1": lambda c, g: g.mc == 1,
+    "the finish kernels' second 64-sample block": lambda c, g: c.B > 64,
+}
+
+
+def test_shapes_cover_the_tiling():
+    assert len(R.SHAPES) == 20 and len(set(R.SHAPES)) == 20 and not set(R.SHAPES) & set(OLD12)
+    for name, hit in BRANCHES.items():
+        assert any(hit(c, R.geo(c)) for c in R.SHAPES), f"no case of SHAPES reaches: {name}"
+    # why the sweep exists: none of the twelve earlier geometries takes any of the first five
+    for name in list(BRANCHES)[:5]:
+        assert not any(BRANCHES[name](c, R.geo(c)) for c in OLD12), f"an earlier case already reaches: {name}"
+    assert all(_mc(c) == R.geo(c).mc for c in R.SHAPES)
+    # what the single cases are listed for (tests/_convbwd64.py's comments)
+    G = [R.geo(c) for c in R.SHAPES]
+    assert (G[0].ntg, G[0].nag, R.SHAPES[0].k - 4) == (2, 2, 1) and (G[1].nag, G[1].R) == (2, 16) and (G[2].nag, G[2].nft) == (3, 2)
+    assert (G[3].nchunks, G[3].cps, G[3].nsl, G[3].nrows % G[3].R) == (7, 2, 4, 2)
+    assert (G[5].R, G[5].nsl) == (8, 2) and (G[6].ntg, G[6].tiles) == (2, 98) and (G[7].R, G[7].run) == (8, 32)
+    assert (G[8].WL, G[8].nseg, G[8].mc, G[8].ntg) == (32, 2, 63, 2) and (G[9].mc, G[9].WLP, G[9].R, G[9].nsl) == (33, 34, 1, 7)
+    assert (G[10].nseg, G[10].nsl) == (2, 16) and (G[11].mc, G[11].nsl) == (71, 21) and (G[12].nchunks, G[12].cps, G[12].nsl) == (8712, 1089, 8)
+    assert G[17].tiles == 1 and (G[18].WLP, G[18].WL) == (2, 1)
+    # every tensor stays small: a case takes well under a second on the device
+    for c in R.SHAPES:
+        assert max(np.prod(R.x_shape(c)), np.prod(R.y_shape(c)), np.prod(R.weight_shape(c))) < 600_000
+
+
+@pytest.mark.parametrize("c", R.SHAPES, ids=R.case_id)
+def test_tiling_mutants_fail_the_comparison(c):
+    """the last K slice dropped (a wrong cend) or the second tap group dropped (a wrong tw0 mask): on random data each falls outside the
+    DEVICE test's bound32 on every case it applies to (nsl > 1, respectively k >= 5), and the true formula stays inside.
+    The data are the device test's: normal draws with R.data_mean's mean 1, so that a sum grows like K and the any-order bound, which
+    grows like K^2 u, stays below it at every K of the sweep.  On zero-mean data the 3D segment case (K = 66^3) could not reject
+    "drop_tail_slice": there the bound is 1 / 0.646 of the largest |grad_w| and the missing slice moves no element by more than 0.162 of
+    it; with the mean it is 5.6 bounds outside, the smallest figure of all cases (R.data_mean's estimate: 5)."""
+    g = R.geo(c)
+    x, w, scale, shift, _, gy = R.make(c, seed=5, act="none", mean=R.data_mean(c))
+    _, want_w, _, _ = R.autograd64(c, x, w, scale, shift, "none", gy)
+    gs = gy.astype(np.float64) * scale.astype(np.float64).reshape((1, -1) + (1,) * c.nd)
+    gw, K, mag = R.grad_w64(c, x, gs)
+    lim = R.bound32(K, mag)
+    ok = lambda got: bool((np.abs(got - want_w) <= lim).all())
+    assert ok(gw)
+    m = R.tail_slice_mask(c)
+    assert m.any() and (g.nsl == 1) == bool(m.all())
+    rel = lambda d: np.divide(np.abs(d), lim, out=np.zeros_like(lim), where=lim > 0).max()      # (a tap that never meets the grid: 0 / 0)
+    print(f"max |grad_w| / bound {rel(want_w):.3e}")
+    for mutant, applies in (("drop_tail_slice", g.nsl > 1), ("drop_tap_group", c.k >= 5)):
+        if applies:
+            got = R.grad_w64(c, x, gs, mutant=mutant)[0]
+            worst = rel(got - want_w)
+            print(f"{mutant}: max |change| / bound {worst:.3e}")
+            assert not ok(got), f"{mutant} stays inside bound32: max |change| / bound {worst:.3e}"
+
+
+@pytest.mark.parametrize("c", R.SHAPES, ids=R.case_id)
+def test_lattice_sums_of_the_sweep_stay_below_2_24_and_tell_the_mutants(c):
+    """what test_integer_lattice_is_exact (GPU) relies on, checked here first: the float64 sum of |terms| of every element is below 2^24
+    (the largest is the 3D n = 66 case: at most 18 * 66^3 = 5.2 M).  That test asks for equality, and on its data (same seed) both
+    tiling mutants differ from the formula on every case they apply to"""
+    g = R.geo(c)
+    x, _, scale, _, _, gy = R.make(c, seed=7, lattice=True)
+    gs = R.gs32(gy, scale)
+    gw, _, mag = R.grad_w64(c, x, gs)
+    assert mag.max() < 2 ** 24 and np.abs(gy).sum() < 2 ** 24
+    if g.nsl > 1:
+        assert not np.array_equal(R.grad_w64(c, x, gs, mutant="drop_tail_slice")[0], gw)
+    if c.k >= 5:
+        assert not np.array_equal(R.grad_w64(c, x, gs, mutant="drop_tap_group")[0], gw)
+
+
+def test_nan_taps_is_the_formulas_support():
+    """nan_taps against the formula itself: plant one 1.0 in an all-zero F under an all-ones A; grad_w64 is non-zero exactly there"""
+    for c, pos in ((R.SHAPES[4], (0, 11)), (R.SHAPES[15], (14, 7)), (R.SHAPES[16], (8, 0, 4)), (R.SHAPES[9], (130, 64)), (R.CASES[7], (9, 4))):
+        x, gs = np.zeros(R.x_shape(c, 1)), np.ones(R.y_shape(c, 1))
+        Fi = gs if c.op == "deconv" else x
+        if c.op == "deconv":
+            x[:] = 1.0
+            gs[:] = 0.0
+        Fi[(0, 0) + pos] = 1.0
+        gw = R.grad_w64(c, x, gs)[0]
+        assert np.array_equal(gw[0, 0] != 0, R.nan_taps(c, pos)), (c, pos)
+        assert not gw[:, 1:].any()
 
 
 def test_grad_shift_order_is_the_head_backwards():

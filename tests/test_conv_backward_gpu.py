@@ -1,7 +1,8 @@
 """s3r_conv_backward on the device, through the C-ABI in guarded, poisoned buffers unless stated: gs and grad_shift bit for bit against
 tests/_convbwd64.py's restatement, grad_w per element within bound32(K, sum|term|) of float64 and exactly equal on integer lattices,
 run / address / scratch-content / output-subset invariance, the batch-composition rule of the header, grad_x through the adjoint layer's
-forward, refusals that enqueue nothing, the module level (d3 + d4 under VoxelBCELoss against float64 autograd, a three-step SGD loop run
+forward — each over the twelve original geometries and over the tiling sweep R.SHAPES (every branch of convbwd_geo and of the GEMM
+kernel's masks) —, the rule that what lies beyond the tensors is replaced by 0 and not multiplied by 0 (one planted NaN), refusals that enqueue nothing, the module level (d3 + d4 under VoxelBCELoss against float64 autograd, a three-step SGD loop run
 twice, trunk_features), and the profiler record.
 
 There is no measured tolerance in this file."""
@@ -24,6 +25,7 @@ POISON = G._BITS[F32][2]
 INVALID, WORKSPACE = -1, -3
 
 RUNS = [(c, a) for i, c in enumerate(R.CASES) for a in R.acts_of(i)] + [(c, a) for c in R.D3 + R.LONG_ROWS for a in ("none", "relu")]
+RUNS += [(c, a) for c in R.SHAPES for a in ("none", "relu")] + [(R.SHAPES[i], "sigmoid") for i in R.SHAPES_SIGMOID]
 _ids = lambda r: f"{R.case_id(r[0])}-{r[1]}"
 NAMES = ("gs", "grad_w", "grad_shift")
 
@@ -103,8 +105,9 @@ def run(s3r, lib, c, act, x, y, gy, scale, need=(True, True, True), fill="nan", 
 
 @functools.lru_cache(maxsize=None)
 def random_case(c, act):
-    """inputs and references of a (case, act), computed once and shared (left unchanged by the tests)"""
-    x, w, scale, shift, y, gy = R.make(c, seed=31 * R.out_edge(c) + c.cin + c.B, act=act)
+    """inputs and references of a (case, act), computed once and shared (left unchanged by the tests).  The sweep's x and grad_y have
+    mean 1 (R.data_mean: on zero-mean data the any-order bound exceeds the gradient itself from K of about 10^5 on)"""
+    x, w, scale, shift, y, gy = R.make(c, seed=31 * R.out_edge(c) + c.cin + c.B, act=act, mean=R.data_mean(c))
     if act == "none":
         y = None
     g = R.g32(y, gy, act)
@@ -124,8 +127,9 @@ def test_random_data_bit_for_bit_and_against_float64(s3r, lib, r):
     _same_bits(gb, k["gb"], "grad_shift")
     ref, K, mag = k["f64"]
     err, lim = np.abs(gw.astype(np.float64) - ref), R.bound32(K, mag)
-    print(f"grad_w max err / bound {(err / lim).max():.3e}, max |grad_w| {np.abs(ref).max():.3e}")
-    assert (err <= lim).all(), f"worst at {np.unravel_index((err / lim).argmax(), err.shape)}: {(err / lim).max()}"
+    ratio = np.divide(err, lim, out=np.where(err > 0, np.inf, 0.0), where=lim > 0)      # (a tap that never meets the grid has bound 0: it must be 0)
+    print(f"grad_w max err / bound {ratio.max():.3e}, max |grad_w| {np.abs(ref).max():.3e}")
+    assert (err <= lim).all(), f"worst at {np.unravel_index(ratio.argmax(), err.shape)}: {ratio.max()}"
 
 
 @pytest.mark.parametrize("r", RUNS, ids=_ids)
@@ -163,6 +167,8 @@ def test_no_activation_and_no_scale_reads_grad_y_itself(s3r, lib, c):
 
 # ---------------------------------------------------------------- invariance
 STABLE = [(c, "relu") for c in R.CASES] + [(R.CASES[5], "sigmoid"), (R.D3[0], "relu"), (R.LONG_ROWS[0], "none")]
+# of the sweep: the ragged last slice (k6 s2 n40), a halved run (3D k4 s4), stride-2 segments (n141), the second 64-sample block (B = 70)
+STABLE += [(R.SHAPES[3], "relu"), (R.SHAPES[5], "relu"), (R.SHAPES[11], "relu"), (R.SHAPES[19], "relu")]
 
 
 @pytest.mark.parametrize("r", STABLE, ids=_ids)
@@ -190,14 +196,17 @@ def test_runs_addresses_scratch_contents_and_output_subsets_do_not_matter(s3r, l
                 assert a is None
 
 
-@pytest.mark.parametrize("c", [R.CASES[3], R.CASES[0]._replace(B=5), R.CASES[6]._replace(B=5)], ids=R.case_id)
+@pytest.mark.parametrize("c", [R.CASES[3], R.CASES[0]._replace(B=5), R.CASES[6]._replace(B=5),
+                               R.SHAPES[3]._replace(B=3), R.SHAPES[0]._replace(B=3), R.SHAPES[19]], ids=R.case_id)
 def test_a_batch_is_the_ascending_sum_of_its_samples(s3r, lib, c):
     """the header's order: per element, a sample's slabs in ascending slice order, then the per-sample partials in ascending b starting
     from sample 0's.  A B = 1 call returns the sample's partial, so the batch's grad_w (and grad_shift) is the ascending fp32 sum of the
-    B = 1 results — which can hold only when the slicing does not depend on the batch."""
-    assert c.B == 5
+    B = 1 results — which can hold only when the slicing does not depend on the batch.  Of the sweep: the ragged last slice and the two
+    128-row groups at B = 3, and B = 70 (the finish kernels' second block of 64 samples), where grad_shift is the restated order's too."""
+    assert c.B in (3, 5, 70)
     k = random_case(c, "relu")
     _, gw, gb = run(s3r, lib, c, "relu", k["x"], k["y"], k["gy"], k["scale"])
+    _same_bits(gb, k["gb"], "grad_shift against the restated order")
     accw = accb = None
     for b in range(c.B):
         one = slice(b, b + 1)
@@ -207,6 +216,42 @@ def test_a_batch_is_the_ascending_sum_of_its_samples(s3r, lib, c):
         accb = gb1 if accb is None else (accb + gb1).astype(np.float32)
     _same_bits(gw, accw, "grad_w")
     _same_bits(gb, accb, "grad_shift")
+
+
+# ---------------------------------------------------------------- what lies beyond the tensors is replaced, not multiplied
+# odd mc with a pad column (mc 33, WLP 34); a short last chunk (7 chunks of 3 rows over 20); a short last segment of a ConvTranspose
+# (70 = 64 + 6); two 128-row groups with a partial f tile (Ca 130, Cf 3)
+NAN_CASES = [R.SHAPES[9], R.SHAPES[3], R.SHAPES[10], R.SHAPES[0]]
+
+
+@pytest.mark.parametrize("c", NAN_CASES, ids=R.case_id)
+def test_nan_in_the_fine_tensor_poisons_exactly_its_own_sums(s3r, lib, c):
+    """ONE NaN in F (x of a Conv, grad_y of a ConvTranspose; act none and scale NULL, so gs is grad_y itself).  By the header's formula
+    grad_w[a][f][t] = sum A[b][a][q] F[b][f][q s - p + t] it is a term of grad_w[a][f*][t] for every a and exactly the taps t for which,
+    on every axis, pos + p - t is a multiple of s with quotient in [0, mc) (R.nan_taps, pinned against the formula on the CPU): those
+    are NaN, and EVERY other element has the bits of the clean run — the kernel reads positions, channels and taps beyond the tensors
+    from clamped addresses (channel Cf - 1, position 0: the first planted place) and must replace them by 0, not multiply them by 0.
+    Nothing is planted in A: what a NaN there does against the zero padding is not a stated contract."""
+    x, _, _, _, _, gy = R.make(c, seed=13, act="none", scale=False)
+    call = lambda x, gy: run(s3r, lib, c, "none", x, None, gy, None, need=(False, True, False))[1]
+    clean = call(x, gy)
+    assert np.isfinite(clean).all()
+    fine = gy if c.op == "deconv" else x
+    B, Cf, nf = fine.shape[0], fine.shape[1], fine.shape[2]
+    places = [(0, Cf - 1) + (0,) * c.nd, (B - 1, 0) + (nf - 1,) * c.nd, (0, Cf // 2) + tuple(nf // 2 + i for i in range(c.nd))]
+    hit_any = False
+    for place in places:
+        planted = fine.copy()
+        planted[place] = np.nan
+        got = call(*((x, planted) if c.op == "deconv" else (planted, gy)))
+        want_nan = np.zeros(clean.shape, bool)
+        want_nan[:, place[1]] = R.nan_taps(c, place[2:])
+        hit_any |= bool(want_nan.any())
+        is_nan = np.isnan(got)
+        bad = np.argwhere(is_nan != want_nan)
+        assert bad.size == 0, f"NaN at F{place}: {len(bad)} elements of grad_w are NaN / not NaN against the formula, first at {tuple(bad[0])}"
+        _same_bits(np.where(want_nan, 0, got), np.where(want_nan, 0, clean), f"grad_w outside the sums of F{place}")
+    assert hit_any
 
 
 # ---------------------------------------------------------------- grad_x through the adjoint layer
