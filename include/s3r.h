@@ -30,6 +30,9 @@
  *                                           one pass over the grid, fixed summation orders, no atomics   (README.md:77)
  *   s3r_conv_backward (+ s3r_conv_adjoint_desc) torch autograd's backward of a conv3d / ConvTranspose3d + BN + activation block of the voxel
  *                                           decoder: what `python3 runner.py` runs behind the loss for the up-path (README.md:77)
+ *   s3r_stem_backward                       torch autograd's backward of the encoder's first conv2d + BN + ReLU block with respect to its
+ *                                           parameters, from the 8-bit or fp32 renders in their two tensors: with s3r_conv_backward on
+ *                                           the other seven blocks, what `python3 runner.py` runs behind the loss for the encoder (README.md:5,73-74)
  *   s3r_batchnorm_train_forward / _backward torch.nn.BatchNorm2d/3d in TRAINING mode (batch statistics) + activation and its autograd
  *                                           backward: what trains bn.weight / bn.bias of the conv + BN + ReLU blocks   (README.md:77)
  *   s3r_disparity_wta, s3r_disparity_epe    predicted left / right disparity and its end-point error
@@ -78,7 +81,7 @@ extern "C" {
  * the version stays 8.  s3r_chamfer_backward and s3r_linear_backward (+ its scratch query) likewise; s3r_voxel_bce_forward,
  * s3r_voxel_bce_backward and s3r_head_backward (+ its scratch query) likewise; s3r_conv_adjoint_desc and s3r_conv_backward (+ its scratch
  * query) likewise; s3r_cost_volume_backward likewise; s3r_batchnorm_train_forward and s3r_batchnorm_train_backward (+ their scratch queries)
- * likewise: new entry points only, the version stays 8. */
+ * likewise; s3r_stem_backward (+ its scratch query) likewise: new entry points only, the version stays 8. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -551,6 +554,50 @@ int s3r_conv_adjoint_desc(const s3r_conv_desc* d, s3r_conv_desc* adj);
 int64_t s3r_conv_backward_scratch_elems(const s3r_conv_desc* d);
 int s3r_conv_backward(const s3r_conv_desc* d, const float* x, const float* y, const float* grad_y, const float* scale, float* gs,
                       float* grad_w, float* grad_shift, float* scratch, int64_t scratch_elems, void* hip_stream);
+
+/* Backward of the STEM, the encoder's first layer  y = act(conv2d(X, w; 3 -> 32, k 3, stride 2, pad 1) * scale[o] + shift[o]):  its weight and
+ * shift gradients, read from the renders as the forward reads them.  X is the render: fp32 taken as is (renders_u8 = 0), or 8-bit
+ * (renders_u8 != 0) scaled as the forward scales it, the correctly rounded float32(u) / float32(255).  in_size is any edge >= 1, the output
+ * edge m = (in_size - 1) / 2 + 1.  Images [0, n_left) are read from images_left (n_left,3,in_size,in_size), images [n_left, n_images) from
+ * images_right; images_right NULL: all images are in images_left and n_left must equal n_images.  y, grad_y (n_images,32,m,m) fp32; scale
+ * (32) or NULL for 1 (frozen, as in s3r_conv_backward); grad_w (32,3,3,3), torch's weight shape; grad_shift (32).  act is S3R_ACT_NONE or
+ * S3R_ACT_RELU.  There is no gs output and no input gradient (s3r_conv_backward serves a caller who wants one for fp32 renders).
+ *   g, gs           s3r_conv_backward's: none: g = grad_y;  ReLU: g = (y > 0.f) ? grad_y : 0.f (a NaN y gives 0);  gs = g * scale[o], rounded
+ *                   once; g itself when scale is NULL;
+ *   grad_shift[o] = sum_{image, pos} g, bit for bit, in s3r_conv_backward's order (the head backward's) with S = m^2 positions per (image,
+ *                   channel) row: chunks of 512 consecutive positions, lane L owns the 8 positions 256 j + 4 L + i and adds them in
+ *                   ascending position to a partial that starts as +0.0, the halving tree over the 64 partials, the chunk sums in ascending
+ *                   chunk order per image starting from chunk 0's, the images in ascending index starting from image 0's: the SAME bits
+ *                   s3r_conv_backward returns on the converted, concatenated renders (it is a pass of its own over grad_y and y, run by
+ *                   the same kernels);
+ *   grad_w[o][ci][kh][kw] = sum_{image, oh, ow} gs[image][o][oh][ow] * X[image][ci][2 oh - 1 + kh][2 ow - 1 + kw], X = 0 outside the image,
+ *                   on v_mfma_f32_32x32x2_f32 (M = the 32 channels, N = the 27 taps padded to 32, K = positions; each product rounded
+ *                   once and added to the running sum, an fmaf chain).
+ * Order of grad_w's sum, which IS the contract.  An image's output rows are cut into K slices of r = ceil(m / 32) consecutive rows (the
+ * last may be short): a function of m only, never of n_images, n_left, the render type, the device or an address.  A slice never spans two
+ * images; one wave owns it and adds its positions in ascending (oh, ow) to 32 x 27 sums that start as +0.0.  A finish launch adds, per
+ * element, an image's slices in ascending slice order starting from slice 0's; a second adds the images' partials in ascending image index
+ * starting from image 0's (either is skipped when it has one term).  So: no atomics; the same bits on every run, at every address the
+ * alignment rule allows and with any scratch contents on entry; an image's partial is the same in every batch it appears in — grad_w of a
+ * batch equals, bit for bit, the ascending fp32 sum of the single-image results; the result is the same whether the renders arrive as one
+ * tensor or two, and the same for 8-bit renders and for their host conversion.  Positions beyond a row and elements outside an image are
+ * loaded from clamped addresses and replaced by 0 in BOTH operands (0 * NaN would be NaN).
+ * grad_w and grad_shift may each be NULL: that output is not computed, and the other keeps the bits of the full call; both NULL is
+ * S3R_ERR_INVALID.  y may be NULL when act is none (y NULL with ReLU: S3R_ERR_INVALID).  Outputs are overwritten, never accumulated into.
+ * Render pointers must be 16-byte aligned, as for the forward; every other pointer needs 4-byte alignment only.  n_images >= 0 (0 launches
+ * nothing, writes nothing and returns S3R_OK; the query returns 0); n_left outside [1, n_images] with two tensors, or != n_images with one,
+ * in_size < 1, an activation other than none / ReLU, a tensor >= 2^31 elements or >= 4 GiB: S3R_ERR_INVALID.
+ * `scratch`: s3r_stem_backward_scratch_elems floats (the chunk sums, the slabs, the per-image partials), sized for the worst case over the
+ * outputs asked for, independent of the device, monotone in n_images; a shorter (or NULL) one is S3R_ERR_WORKSPACE.  Nothing is enqueued
+ * when the call is refused.
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new data in the same buffers).
+ * Profiler: ONE record, family 1 (stem), tag 1; `flops` = 2 n_images m^2 32 27 when grad_w is computed, else 0; `bytes` = the tensors the call
+ * must read and write (grad_y; y unless act is none; the renders, scale and grad_w when grad_w is computed; grad_shift). */
+int64_t s3r_stem_backward_scratch_elems(int n_images, int in_size);
+int s3r_stem_backward(const void* images_left, const void* images_right, int n_left, int renders_u8, const float* y, const float* grad_y,
+                      const float* scale, float* grad_w, float* grad_shift, int n_images, int in_size, int act, float* scratch,
+                      int64_t scratch_elems, void* hip_stream);
 
 /* Train-mode BatchNorm (batch statistics) + activation on z (B,C,S) fp32, plain and contiguous; S (`positions`) is the product of the
  * spatial extents, so one entry serves 2D and 3D layers.  gamma, beta, save_mean, save_var, save_invstd, grad_gamma, grad_beta are (C).

@@ -1145,6 +1145,62 @@ int s3r_conv_backward(const s3r_conv_desc* d, const float* x, const float* y, co
     return S3R_OK;
 }
 
+// the stem backward's shape: in_size >= 1, n_images >= 0, y / grad_y (n_images,32,m,m) within the header's limits; fills m
+static int stembwd_dims(int n_images, int in_size, const char* who, int* m_out) {
+    if (n_images < 0 || in_size < 1)
+        return fail(S3R_ERR_INVALID, "%s: n_images >= 0 and in_size >= 1 (n_images %d, in_size %d)", who, n_images, in_size);
+    const int64_t m = (in_size - 1) / 2 + 1;
+    const int64_t Y = (int64_t)n_images * 32 * m * m;
+    if (32 * m * m >= kMaxElems || Y >= kMaxElems || 4 * Y >= kMaxBytes)
+        return fail(S3R_ERR_INVALID, "%s: tensor of 2^31 elements / 4 GiB or more: split the batch", who);
+    *m_out = (int)m;
+    return S3R_OK;
+}
+
+int64_t s3r_stem_backward_scratch_elems(int n_images, int in_size) {
+    int m = 0;
+    int rc = stembwd_dims(n_images, in_size, "s3r_stem_backward_scratch_elems", &m);
+    if (rc) return rc;
+    return s3r::stem_backward_scratch_elems(n_images, m);
+}
+
+int s3r_stem_backward(const void* images_left, const void* images_right, int n_left, int renders_u8, const float* y, const float* grad_y,
+                      const float* scale, float* grad_w, float* grad_shift, int n_images, int in_size, int act, float* scratch,
+                      int64_t scratch_elems, void* hip_stream) {
+    if (!grad_w && !grad_shift)
+        return fail(S3R_ERR_INVALID, "stem backward: grad_w and grad_shift are both NULL (each may be: it is not computed)");
+    if (act != S3R_ACT_NONE && act != S3R_ACT_RELU) return fail(S3R_ERR_INVALID, "s3r_stem_backward takes none / relu (act %d)", act);
+    int m = 0;
+    int rc = stembwd_dims(n_images, in_size, "s3r_stem_backward", &m);
+    if (rc) return rc;
+    if (n_images == 0) return S3R_OK;
+    if (images_right ? (n_left < 1 || n_left > n_images) : n_left != n_images)
+        return fail(S3R_ERR_INVALID, "stem backward: n_left must lie in [1, n_images] with two render tensors and equal n_images with one "
+                                     "(n_left %d, n_images %d)", n_left, n_images);
+    if (!images_left || !grad_y) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    if (act != S3R_ACT_NONE && !y) return fail(S3R_ERR_INVALID, "stem backward: y is NULL (it may be only when act is none)");
+    if ((((uintptr_t)images_left) | ((uintptr_t)images_right)) & 15)
+        return fail(S3R_ERR_INVALID, "render tensors must be 16-byte aligned (got %p, %p)", images_left, images_right);
+    const int64_t P = (int64_t)in_size * in_size;
+    const int64_t big = 3 * P * (n_left > n_images - n_left ? n_left : n_images - n_left);
+    if (big >= kMaxElems || (renders_u8 ? 1 : 4) * big >= kMaxBytes)
+        return fail(S3R_ERR_INVALID, "stem backward: render tensor of 2^31 elements / 4 GiB or more: split the batch");
+    const int64_t need = s3r::stem_backward_scratch_elems(n_images, m);
+    if (!scratch || scratch_elems < need)
+        return fail(S3R_ERR_WORKSPACE, "stem backward needs %lld floats of scratch (s3r_stem_backward_scratch_elems), got %lld",
+                    (long long)need, (long long)(scratch ? scratch_elems : 0));
+    hipStream_t s = (hipStream_t)hip_stream;
+    const double B = n_images, Y = B * 32.0 * (double)m * m;
+    const double flops = grad_w ? 2.0 * B * (double)m * m * 32.0 * 27.0 : 0.0;
+    const double bytes = 4.0 * (Y * (act != S3R_ACT_NONE ? 2.0 : 1.0) + (scale && grad_w ? 32.0 : 0.0) + (grad_w ? 864.0 : 0.0) +
+                                (grad_shift ? 32.0 : 0.0)) + (grad_w ? (renders_u8 ? 1.0 : 4.0) * B * 3.0 * (double)P : 0.0);
+    ProfScope ps(s, F_STEM, 1, flops, bytes);
+    hipError_t e = s3r::launch_stem_backward(images_left, images_right, n_left, renders_u8 != 0, y, grad_y, scale, grad_w, grad_shift,
+                                             n_images, in_size, m, act, scratch, s, &ps.launches);
+    if (e != hipSuccess) return hip_fail(e, "stem backward launch");
+    return S3R_OK;
+}
+
 // z / y / grad_z of a train-mode BatchNorm call within the header's limits (< 2^31 elements, < 4 GiB)
 static int bn_dims(int batch, int channels, int64_t positions) {
     if (batch < 0 || channels <= 0 || positions <= 0)

@@ -311,6 +311,27 @@ int64_t conv_backward_scratch_elems(const ConvBwdGeo& g, int B, int cout, int64_
     return (int64_t)B * cout * S + (int64_t)cout * B * cb_chunks(S) + (nslab > 1 ? nslab * g.slab : 0);
 }
 
+// grad_shift alone, for a caller with a weight-gradient kernel of its own (s3r_stem_bwd.hip): the two launches launch_conv_backward makes
+// for it, the same kernels with the same arguments; part holds cout B ceil(S / 512) floats
+hipError_t launch_convbwd_shift(const float* y, const float* gy, int B, int cout, int64_t S, int act, float* part, float* gshift,
+                                hipStream_t s, int* launches) {
+    const long long nch = cb_chunks(S);
+    const long long waves = (long long)B * cout * nch;
+    const double Y = (double)B * cout * (double)S;
+    {
+        AuxScope aux(s, 4.0 * (Y * (act ? 2.0 : 1.0) + (double)cout * B * nch));
+        hipLaunchKernelGGL(convbwd_prep_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, y, gy, (const float*)nullptr,
+                           (float*)nullptr, part, B, cout, (long long)S, nch, act);
+    }
+    ++*launches;
+    {
+        AuxScope aux(s, 4.0 * ((double)cout * B * nch + cout));
+        hipLaunchKernelGGL(convbwd_shift_finish_kernel, dim3((unsigned)cout), dim3(64), 0, s, part, gshift, B, nch);
+    }
+    ++*launches;
+    return hipGetLastError();
+}
+
 hipError_t launch_conv_backward(const ConvBwdGeo& g, int deconv, const float* x, const float* y, const float* gy, const float* scale,
                                 float* gs, float* gw, float* gshift, int B, int cout, int64_t S, int act, float* scratch, hipStream_t s,
                                 int* launches) {

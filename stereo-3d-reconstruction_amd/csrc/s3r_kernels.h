@@ -326,6 +326,15 @@ int64_t conv_backward_scratch_elems(const ConvBwdGeo& g, int B, int cout, int64_
 hipError_t launch_conv_backward(const ConvBwdGeo& g, int deconv, const float* x, const float* y, const float* gy, const float* scale,
                                 float* gs, float* gw, float* gshift, int B, int cout, int64_t S, int act, float* scratch, hipStream_t s,
                                 int* launches);
+hipError_t launch_convbwd_shift(const float* y, const float* gy, int B, int cout, int64_t S, int act, float* part, float* gshift,
+                                hipStream_t s, int* launches);
+// s3r_stem_bwd.hip: grad_w and grad_shift of the stem (conv2d 3 -> 32, k 3, s 2, p 1) from fp32 or 8-bit renders in one or two tensors;
+// one wave per K slice of stem_bwd_rows(m) output rows, slabs added per image, then over the images, in ascending order
+int stem_bwd_rows(int m);
+int64_t stem_backward_scratch_elems(int B, int m);
+hipError_t launch_stem_backward(const void* left, const void* right, int n_left, int u8, const float* y, const float* gy,
+                                const float* scale, float* gw, float* gshift, int B, int n, int m, int act, float* scratch, hipStream_t s,
+                                int* launches);
 // s3r_cost_volume_bwd.hip: the cost volume's backward, one thread per (b, c, h, w), d ascending; gl or gr may be NULL (not both)
 hipError_t launch_cost_volume_backward(const float* gv, float* gl, float* gr, int B, int C, int D, int H, int W, hipStream_t s);
 // s3r_voxel_loss.hip: BCELoss's per-element rule with a per-sample sum in a fixed order (loss_sum or loss_elem may be NULL), and its

@@ -423,7 +423,7 @@ class _HipChain(nn.Module):
         `differentiable_batchnorm(z, blk.bn, layer.act)`: batch statistics, gradients to `bn.weight` and `bn.bias`, the running
         statistics updated.  Layers without a BatchNorm are unchanged."""
         n_in = self._sizes()[first][0]
-        x = _check_input(x, "x", (self._layers[first].cin,) + (n_in,) * 3)
+        x = _check_input(x, "x", (self._layers[first].cin,) + (n_in,) * spec.ndim(self._layers[first]))
         for l in self._layers[first:stop]:
             blk: _Block = getattr(self, l.name)
             if batch_stats and blk.bn is not None:
@@ -513,6 +513,47 @@ class Encoder(_HipChain):
         if left.shape[0] == 0:
             return self._run(left)
         return self._run(left, None, 0, right)
+
+    # -- the trainable tower (fp32 models) --------------------------------------------------------------
+    def _differentiable(self, left: torch.Tensor, right: Optional[torch.Tensor], batch_stats: bool, who: str) -> torch.Tensor:
+        if self.precision != "fp32":
+            raise RuntimeError(f"{who} is implemented for fp32 models only (this one is {self.precision}): the backward kernels read "
+                               "fp32 activations")
+        n = left.shape[0] + (right.shape[0] if right is not None else 0)
+        if n == 0 or n > 2 * MAX_CHUNK:
+            raise RuntimeError(f"{who} takes 1 .. {MAX_CHUNK} pairs ({2 * MAX_CHUNK} images) per call, got {n} images: split the batch")
+        l = self._layers[0]
+        blk: _Block = getattr(self, l.name)
+        if batch_stats:
+            z = _StemFunction.apply(blk.conv.weight, blk.conv.bias, None, self, left, right, "none")
+            x = differentiable_batchnorm(z, blk.bn, l.act)
+        else:
+            scale, _ = blk.folded()
+            shift = blk.bn.bias + (blk.conv.bias - blk.bn.running_mean.detach()) * scale
+            x = _StemFunction.apply(blk.conv.weight, shift, scale, self, left, right, l.act)
+        return self._differentiable_layers(x, 1, len(self._layers), batch_stats)
+
+    def differentiable_pair(self, left: torch.Tensor, right: torch.Tensor, batch_stats: bool = False) -> torch.Tensor:
+        """`forward_pair` recorded for autograd on this module's OWN parameters: features (2B,32,28,28), left batch first; B <= MAX_CHUNK
+        pairs, fp32 models only.  e1 runs as `_StemFunction`: the stem kernel's forward on the renders as given (8-bit or fp32, in their
+        two tensors: the one-layer chain `_run(left, "e1", 0, right)`), and `stem_backward` (`s3r_stem_backward`) behind it — no input
+        gradient: nothing upstream of a render is trained.  e2 .. e8 run as `differentiable_conv`, one call each
+        (`_differentiable_layers`).  By default every BatchNorm stays in eval mode and folded: `bn.weight` and the running statistics
+        are frozen, the shift expression bn.bias + (conv.bias - running_mean) * scale is evaluated under grad, as on the decoder's path.
+        batch_stats=True runs every block as torch runs it in training mode: the convolution without scale and activation, then
+        `differentiable_batchnorm` with the statistics of all 2B images (what the reference's `encoder(torch.cat([left, right]))` does in
+        training mode); `bn.weight` and `bn.bias` get gradients and the running statistics are updated.  The stem's forward kernel has
+        no form without its activation, so e1's forward then goes through `conv_forward` (the general route) on the fp32 conversion of
+        the concatenated renders, while its backward still is `s3r_stem_backward` (act none) on the renders as given."""
+        left = _check_render(left, "left")
+        right = _check_render(right, "right")
+        if left.shape[0] != right.shape[0] or left.device != right.device or left.dtype != right.dtype:
+            raise RuntimeError("left and right must be two batches of one size and dtype on one device")
+        return self._differentiable(left, right, batch_stats, "Encoder.differentiable_pair")
+
+    def differentiable(self, images: torch.Tensor, batch_stats: bool = False) -> torch.Tensor:
+        """`forward` recorded for autograd on one tensor of renders (N <= 2 MAX_CHUNK images): see `differentiable_pair`."""
+        return self._differentiable(_check_render(images, "images"), None, batch_stats, "Encoder.differentiable")
 
 
 class CostVolume(nn.Module):
@@ -931,6 +972,16 @@ class Stereo2Voxel(_DisparityMixin, nn.Module):
         outs = list(self._decoded(left, right))
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
+    def differentiable(self, left: torch.Tensor, right: torch.Tensor, batch_stats: bool = False) -> torch.Tensor:
+        """The whole network recorded for autograd on its own parameters: (B,32,32,32) occupancy, B <= MAX_CHUNK, fp32 models only.
+        `encoder.differentiable_pair`, `cost_volume.differentiable`, `decoder.differentiable_tail(start="v1")` — every stage on its
+        plain standalone kernels, so the value agrees with `forward` (which fuses hand-offs) to fp32 rounding, not bit for bit.
+        A training step: `VoxelBCELoss()(model.differentiable(l, r), gt).backward()`.  batch_stats: see `Encoder.differentiable_pair`."""
+        self.decoder._fp32_only("Stereo2Voxel.differentiable")
+        feats = self.encoder.differentiable_pair(left, right, batch_stats)
+        b = feats.shape[0] // 2
+        return self.decoder.differentiable_tail(self.cost_volume.differentiable(feats[:b], feats[b:]), "v1", batch_stats)
+
     @torch.no_grad()
     def trunk_features(self, left: torch.Tensor, right: torch.Tensor, upto: str = "d2") -> torch.Tensor:
         """The frozen trunk — encoder, cost volume, decoder up to the layer `upto` (any decoder layer in front of d4) — without a graph:
@@ -1006,6 +1057,16 @@ class Stereo2Point(_DisparityMixin, nn.Module):
     def forward(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
         outs = [self.point_head(latent) for latent in self._latents(left, right)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    def differentiable(self, left: torch.Tensor, right: torch.Tensor, batch_stats: bool = False) -> torch.Tensor:
+        """The whole network recorded for autograd on its own parameters: (B,2048,3) points, B <= MAX_CHUNK, fp32 models only.
+        `encoder.differentiable_pair`, `cost_volume.differentiable`, `decoder.differentiable_features(start="v1")`,
+        `point_head.differentiable`.  A training step: `ChamferDistance()(model.differentiable(l, r), target)`, then `.backward()` on
+        the loss built from it.  batch_stats: see `Encoder.differentiable_pair`."""
+        feats = self.encoder.differentiable_pair(left, right, batch_stats)
+        b = feats.shape[0] // 2
+        latent = self.decoder.differentiable_features(self.cost_volume.differentiable(feats[:b], feats[b:]), "v1", batch_stats)
+        return self.point_head.differentiable(latent)
 
     @torch.no_grad()
     def latent(self, left: torch.Tensor, right: torch.Tensor) -> torch.Tensor:
@@ -1604,6 +1665,102 @@ def differentiable_conv(x: torch.Tensor, weight: torch.Tensor, scale: Optional[t
     `conv_backward`, called with exactly the sides autograd needs (`needs_input_grad` of x, weight and shift).  `scale` is frozen: its
     gradient is `None` (a folded BatchNorm scale: `bn.weight` is not trained through this path)."""
     return _ConvFunction.apply(x, weight, scale, shift, layer)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The stem's backward: s3r_stem_backward
+def _check_stem_render(x, name):
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] < 1:
+        raise RuntimeError(f"{name} must be renders (N, 3, n, n), got {tuple(getattr(x, 'shape', ()))}")
+    dt = torch.uint8 if x.dtype == torch.uint8 else torch.float32
+    return _aligned16(_check_input(x.detach(), name, x.shape[1:], dt))
+
+
+@torch.no_grad()
+def stem_backward(left: torch.Tensor, right: Optional[torch.Tensor], y: Optional[torch.Tensor], grad_y: torch.Tensor,
+                  scale: Optional[torch.Tensor] = None, act: str = "relu", need_w: bool = True, need_shift: bool = True):
+    """(grad_w, grad_shift) of the stem y = act(conv2d(X, w; 3 -> 32, k 3, s 2, p 1) * scale + shift) for the output gradient grad_y
+    (N,32,m,m), `None` for the side not asked for: ONE `s3r_stem_backward` call.  X are the renders as the forward reads them, float32
+    or uint8 (scaled by 1/255 as they are read), `left` then `right` (None: one tensor) — no conversion, no concatenation.  Fixed
+    summation orders, no atomics: the same bits for one tensor or two, for uint8 renders and their host conversion, and grad_w of a batch
+    is the ascending sum of its images' results.  y may be None when act is "none"; scale (32) is frozen."""
+    if act not in ("none", "relu"):
+        raise RuntimeError(f"stem_backward: act must be 'none' or 'relu', got {act!r}")
+    if not (need_w or need_shift):
+        raise RuntimeError("stem_backward needs need_w or need_shift")
+    left = _check_stem_render(left, "left")
+    n, dev = left.shape[2], left.device
+    if right is not None:
+        right = _check_stem_render(right, "right")
+        if tuple(right.shape[1:]) != tuple(left.shape[1:]) or right.dtype != left.dtype or right.device != dev:
+            raise RuntimeError("left and right renders must share one edge, dtype and device")
+        if right.shape[0] == 0:
+            right = None
+        elif left.shape[0] == 0:
+            left, right = right, None
+    N = left.shape[0] + (right.shape[0] if right is not None else 0)
+    m = (n - 1) // 2 + 1
+    gy = _check_input(grad_y, "grad_y", (32, m, m))
+    if gy.shape[0] != N:
+        raise RuntimeError(f"grad_y must hold {N} images, got {gy.shape[0]}")
+    yy = None
+    if act != "none":
+        if y is None:
+            raise RuntimeError(f"stem_backward: act {act!r} needs the layer's output y")
+        yy = _check_input(y.detach(), "y", (32, m, m))
+        if yy.shape[0] != N:
+            raise RuntimeError(f"y must hold {N} images, got {yy.shape[0]}")
+    sc = _check_channel_vector(scale, 32, dev, "stem_backward", "scale")
+    gw = torch.empty((32, 3, 3, 3), dtype=torch.float32, device=dev) if need_w else None
+    gb = torch.empty((32,), dtype=torch.float32, device=dev) if need_shift else None
+    if N == 0:                                     # an empty sum
+        for t in (gw, gb):
+            if t is not None:
+                t.zero_()
+        return gw, gb
+    lib = _lib.load()
+    need = _lib.check(lib.s3r_stem_backward_scratch_elems(N, n), "stem backward scratch query")
+    scratch = torch.empty(max(need, 1), dtype=torch.float32, device=dev)
+    ptr = [None if t is None else t.data_ptr() for t in (yy, gy, sc, gw, gb)]
+    _lib.check(lib.s3r_stem_backward(left.data_ptr(), right.data_ptr() if right is not None else None, left.shape[0],
+                                     int(left.dtype == torch.uint8), *ptr, N, n, _lib.ACT[act], scratch.data_ptr(), scratch.numel(),
+                                     _stream_ptr(dev)), "stem backward")
+    return gw, gb
+
+
+class _StemFunction(torch.autograd.Function):
+    """The encoder's first block with `stem_backward` as its derivative with respect to (weight, shift); the renders get no gradient.
+    act "relu": the stem kernel itself on the renders as given — the one-layer chain `encoder._run(left, "e1", 0, right)`, which reads the
+    encoder's own e1 parameters (`weight`, `shift` and `scale` ARE those, handed in so that autograd sees them).  act "none" (the
+    batch-statistics form; scale None, shift = conv.bias): the stem kernel has no form without its activation, so the forward is
+    `conv_forward` on the fp32 conversion of the concatenated renders; the backward reads the renders as given either way."""
+
+    @staticmethod
+    def forward(ctx, weight, shift, scale, encoder, left, right, act):
+        if act == "none":
+            x = left if right is None else torch.cat([left, right], 0)
+            if x.dtype == torch.uint8:                             # IEEE division by a device tensor: the kernels' correctly rounded u / 255
+                x = x.float() / torch.full((), 255.0, device=x.device)     # (a Python-scalar divisor may be turned into a reciprocal)
+            y = conv_forward(x, weight, None, shift, dataclasses.replace(encoder._layers[0], act="none"))
+        else:
+            y = encoder._run(left, encoder.names[0], 0, right)
+        ctx.act, ctx.has_scale, ctx.has_right = act, scale is not None, right is not None
+        ctx.save_for_backward(left, y, *((right,) if right is not None else ()), *((scale,) if scale is not None else ()))
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        saved = list(ctx.saved_tensors)
+        left, y = saved[0], saved[1]
+        right = saved[2] if ctx.has_right else None
+        scale = saved[-1] if ctx.has_scale else None
+        need_w, need_shift = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_w or need_shift):
+            return (None,) * 7
+        gw, gb = stem_backward(left, right, y if ctx.act != "none" else None, grad_y.contiguous().float(), scale, ctx.act, need_w,
+                               need_shift)
+        return gw, gb, None, None, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
