@@ -3,21 +3,16 @@
 // of the adjoint layer (s3r_conv_adjoint_desc) on gs.  Three results, each optional, each with a FIXED order — no atomics, the same bits
 // on every run and at every 4-byte-aligned address:
 //
-//   g  (B,cout,S)  the pre-activation gradient, fp32, nothing fused — s3r_linear_backward's rule:
-//       none: g = grad_y        ReLU: g = (y > 0.f) ? grad_y : 0.f  (a NaN y gives 0)        sigmoid: t = 1 - y; u = y * t; g = grad_y * u
+//   g  (B,cout,S)  the pre-activation gradient, fp32, nothing fused: act_grad (s3r_ordered.h)
 //   gs = g * scale[o], rounded once (g itself when scale is NULL)                                                (convbwd_prep_kernel)
-//   grad_shift[o] = sum_{b,s} g[b][o][s]   the head backward's order with channel o's S positions of a sample in place of the sample's
+//   grad_shift[o] = sum_{b,s} g[b][o][s]   s3r_ordered.h's order, a row being channel o's S positions of one sample
 //                                                                                     (convbwd_prep_kernel + convbwd_shift_finish_kernel)
 //   grad_w[a][f][t] = sum_{b, q} A[b][a][q] F[b][f][q s - p + t]   (F reads 0 outside its grid)    (convbwd_gw_kernel + convbwd_finish_kernel)
 //       q runs over the COARSE grid (a Conv's output, a ConvTranspose's input), A lives on it with Ca channels, F on the fine grid with
 //       Cf channels:  Conv: A = gs, F = x -> [cout][cin][k..];  ConvTranspose: A = x, F = gs -> [cin][cout][k..]: torch's layouts.
 //
-// convbwd_prep_kernel: a WAVE owns one chunk of 512 consecutive positions of one (sample, channel) row; lane L owns the eight positions
-//   256 j + 4 L + i (j = 0, 1; i = 0..3), two 16-byte accesses per tensor through a dword-aligned vector type (s3r_head_bwd.hip's
-//   scheme: a chunk that crosses the row's end goes element by element, a wave-uniform choice, same arithmetic).  It stores gs and
-//   the chunk's sum of g (lane partial from +0.0 in ascending position, halving tree over the 64 lanes) to part[o][b][chunk].
-//   convbwd_shift_finish_kernel: one wave per channel; per sample the chunk sums in ascending chunk order starting from chunk 0's, then
-//   the samples in ascending b starting from sample 0's.
+// convbwd_prep_kernel: a WAVE owns one chunk of one (sample, channel) row (s3r_ordered.h); it stores gs and the chunk's sum of g to
+//   part[o][b][chunk].  convbwd_shift_finish_kernel: one wave per channel, row_total of part[o].
 //
 // convbwd_gw_kernel: the GEMM M = Ca, N = Cf k^nd, K = B Q on v_mfma_f32_32x32x2_f32.  Both operands are position-contiguous and
 //   channel-strided, so a fragment (32 channels at one position) is strided in memory: tiles [channels][a run of positions] go through
@@ -36,46 +31,15 @@
 //   slab 0, and the per-sample partials in ascending b starting from sample 0's.  One slab in all (B = 1, nsl = 1) is written straight to grad_w.
 //
 // All indexing is 64-bit element arithmetic on plain pointers; the grids are one-dimensional.
-#include "s3r_kernels.h"
+#include "s3r_ordered.h"
 
 namespace s3r {
 
 typedef float f32x16_c __attribute__((ext_vector_type(16)));
-typedef float v4f_c __attribute__((ext_vector_type(4)));
-typedef float v4f_cu __attribute__((ext_vector_type(4), aligned(4)));      // dword-aligned 16-byte access
-
-constexpr int CB_CHUNK = 512;        // positions per wave of the prep pass (the head backward's chunk)
-constexpr int CB_Q = CB_CHUNK / 256;
 constexpr int CB_AG = 128;           // rows a per workgroup (4 waves x 32)
 constexpr int CB_FT = 32;            // channels f per workgroup
 constexpr int CB_RUN = 64;           // coarse positions per staged chunk (upper bound)
 constexpr int CB_LDS_MAX = 64 * 1024;
-
-__device__ __forceinline__ v4f_c cb_load4(const float* __restrict__ p, long long i, long long n, bool full) {
-    if (full) return *reinterpret_cast<const v4f_cu*>(p + i);
-    v4f_c v;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = i + k < n ? p[i + k] : 0.f;
-    return v;
-}
-
-__device__ __forceinline__ void cb_store4(float* __restrict__ p, long long i, long long n, v4f_c v, bool full) {
-    if (full) { *reinterpret_cast<v4f_cu*>(p + i) = v; return; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (i + k < n) p[i + k] = v[k];
-}
-
-__device__ __forceinline__ float cb_g(float y, float gy, int act) {
-#pragma clang fp contract(off)
-    if (act == 1) return (y > 0.f) ? gy : 0.f;
-    if (act == 2) {
-        const float t = 1.f - y;
-        const float u = y * t;
-        return gy * u;
-    }
-    return gy;
-}
 
 // y, gy (B,Co,S); gs (B,Co,S) or NULL; part [Co][B][nch] chunk sums of g or NULL
 __global__ __launch_bounds__(256) void convbwd_prep_kernel(const float* __restrict__ y, const float* __restrict__ gy,
@@ -87,32 +51,32 @@ __global__ __launch_bounds__(256) void convbwd_prep_kernel(const float* __restri
     if (wid >= (long long)B * Co * nch) return;                          // (wave-uniform; the kernel has no barrier)
     const long long row = wid / nch, k = wid - row * nch;
     const long long b = row / Co, o = row - b * Co;
-    const long long s0 = k * CB_CHUNK + 4 * lane;
-    const bool full = (k + 1) * CB_CHUNK <= S;                           // (wave-uniform)
+    const long long s0 = k * CHUNK + 4 * lane;
+    const bool full = (k + 1) * CHUNK <= S;                           // (wave-uniform)
     const float sc = scale ? scale[o] : 1.f;
     const float* __restrict__ gr = gy + (size_t)row * S;
-    v4f_c gv[CB_Q], yv[CB_Q];
+    v4f gv[Q], yv[Q];
 #pragma unroll
-    for (int j = 0; j < CB_Q; ++j) {
-        gv[j] = cb_load4(gr, s0 + 256 * j, S, full);
-        yv[j] = act ? cb_load4(y + (size_t)row * S, s0 + 256 * j, S, full) : v4f_c{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < Q; ++j) {
+        gv[j] = load4(gr, s0 + 256 * j, S, full);
+        yv[j] = act ? load4(y + (size_t)row * S, s0 + 256 * j, S, full) : v4f{0.f, 0.f, 0.f, 0.f};
     }
     float a = 0.f;
 #pragma unroll
-    for (int j = 0; j < CB_Q; ++j) {
-        v4f_c out;
+    for (int j = 0; j < Q; ++j) {
+        v4f out;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const bool in = s0 + 256 * j + i < S;
-            const float v = cb_g(yv[j][i], gv[j][i], act);
+            const float v = act_grad(yv[j][i], gv[j][i], act);
             out[i] = scale ? v * sc : v;
             a = a + (in ? v : 0.f);
         }
-        if (gs) cb_store4(gs + (size_t)row * S, s0 + 256 * j, S, out, full);
+        if (gs) store4(gs + (size_t)row * S, s0 + 256 * j, S, out, full);
     }
     if (part) {
 #pragma unroll
-        for (int w = 32; w > 0; w >>= 1) a = a + __shfl_down(a, w, 64);
+        for (int w = 32; w > 0; w >>= 1) a = a + __shfl_down(a, w, 64);   // (wave_tree's adds, kept open-coded: the call changes this kernel's machine code)
         if (lane == 0) part[((size_t)o * B + b) * nch + k] = a;
     }
 }
@@ -122,21 +86,7 @@ __global__ __launch_bounds__(64) void convbwd_shift_finish_kernel(const float* _
                                                                   long long nch) {
 #pragma clang fp contract(off)
     const int o = blockIdx.x, lane = threadIdx.x;
-    float acc = 0.f;
-    for (int b0 = 0; b0 < B; b0 += 64) {
-        const int b = b0 + lane;
-        float p = 0.f;
-        if (b < B) {
-            const float* __restrict__ src = part + ((size_t)o * B + b) * nch;
-            p = src[0];
-            for (long long z = 1; z < nch; ++z) p = p + src[z];
-        }
-        const int n = B - b0 < 64 ? B - b0 : 64;
-        for (int l = 0; l < n; ++l) {
-            const float v = __shfl(p, l, 64);
-            acc = (b0 + l == 0) ? v : acc + v;
-        }
-    }
+    const float acc = row_total(part + (size_t)o * B * nch, B, nch, lane);
     if (lane == 0) gshift[o] = acc;
 }
 
@@ -303,32 +253,30 @@ bool convbwd_geo(int deconv, int nd, int cin, int cout, int in_size, int out_siz
     return true;
 }
 
-static long long cb_chunks(long long S) { return (S + CB_CHUNK - 1) / CB_CHUNK; }
-
 // [gs: B cout S][chunk sums of g: cout B ceil(S / 512)][slabs: B nsl Ca Cf T when B nsl > 1] — the worst case over the outputs
 int64_t conv_backward_scratch_elems(const ConvBwdGeo& g, int B, int cout, int64_t S) {
     const long long nslab = (long long)B * g.nsl;
-    return (int64_t)B * cout * S + (int64_t)cout * B * cb_chunks(S) + (nslab > 1 ? nslab * g.slab : 0);
+    return (int64_t)B * cout * S + (int64_t)cout * B * chunks(S) + (nslab > 1 ? nslab * g.slab : 0);
 }
 
-// grad_shift alone, for a caller with a weight-gradient kernel of its own (s3r_stem_bwd.hip): the two launches launch_conv_backward makes
-// for it, the same kernels with the same arguments; part holds cout B ceil(S / 512) floats
-hipError_t launch_convbwd_shift(const float* y, const float* gy, int B, int cout, int64_t S, int act, float* part, float* gshift,
-                                hipStream_t s, int* launches) {
-    const long long nch = cb_chunks(S);
+// gs (when non-NULL) and grad_shift (when non-NULL; part: cout B ceil(S / 512) floats): the prep pass and the row totals.  A caller with a
+// weight-gradient kernel of its own (s3r_stem_bwd.hip) asks for grad_shift alone, scale = gs = NULL
+hipError_t launch_convbwd_prep(const float* y, const float* gy, const float* scale, float* gs, float* gshift, int B, int cout, int64_t S,
+                               int act, float* part, hipStream_t s, int* launches) {
+    const long long nch = chunks(S);
     const long long waves = (long long)B * cout * nch;
     const double Y = (double)B * cout * (double)S;
     {
-        AuxScope aux(s, 4.0 * (Y * (act ? 2.0 : 1.0) + (double)cout * B * nch));
-        hipLaunchKernelGGL(convbwd_prep_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, y, gy, (const float*)nullptr,
-                           (float*)nullptr, part, B, cout, (long long)S, nch, act);
+        AuxScope aux(s, 4.0 * (Y * (act ? 2.0 : 1.0) + (scale ? cout : 0) + (gs ? Y : 0.0) + (gshift ? (double)cout * B * nch : 0.0)));
+        hipLaunchKernelGGL(convbwd_prep_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, y, gy, scale, gs,
+                           gshift ? part : nullptr, B, cout, (long long)S, nch, act);
     }
     ++*launches;
-    {
+    if (gshift) {
         AuxScope aux(s, 4.0 * ((double)cout * B * nch + cout));
         hipLaunchKernelGGL(convbwd_shift_finish_kernel, dim3((unsigned)cout), dim3(64), 0, s, part, gshift, B, nch);
+        ++*launches;
     }
-    ++*launches;
     return hipGetLastError();
 }
 
@@ -336,7 +284,7 @@ hipError_t launch_conv_backward(const ConvBwdGeo& g, int deconv, const float* x,
                                 float* gs, float* gw, float* gshift, int B, int cout, int64_t S, int act, float* scratch, hipStream_t s,
                                 int* launches) {
     *launches = 0;
-    const long long nch = cb_chunks(S);
+    const long long nch = chunks(S);
     float* gs_buf = scratch;
     float* part = scratch + (size_t)B * cout * S;
     float* slabs = part + (size_t)cout * B * nch;
@@ -348,19 +296,8 @@ hipError_t launch_conv_backward(const ConvBwdGeo& g, int deconv, const float* x,
         else gs_out = gs_buf, gsr = gs_buf;
     }
     if (gs_out || gshift) {
-        const long long waves = (long long)B * cout * nch;
-        const double Y = (double)B * cout * (double)S;
-        {
-            AuxScope aux(s, 4.0 * (Y * (act ? 2.0 : 1.0) + (scale ? cout : 0) + (gs_out ? Y : 0.0) + (gshift ? (double)cout * B * nch : 0.0)));
-            hipLaunchKernelGGL(convbwd_prep_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, y, gy, scale, gs_out,
-                               gshift ? part : nullptr, B, cout, (long long)S, nch, act);
-        }
-        ++*launches;
-        if (gshift) {
-            AuxScope aux(s, 4.0 * ((double)cout * B * nch + cout));
-            hipLaunchKernelGGL(convbwd_shift_finish_kernel, dim3((unsigned)cout), dim3(64), 0, s, part, gshift, B, nch);
-            ++*launches;
-        }
+        hipError_t e = launch_convbwd_prep(y, gy, scale, gs_out, gshift, B, cout, S, act, part, s, launches);
+        if (e != hipSuccess) return e;
     }
     if (gw) {
         const float* A = deconv ? x : gsr;

@@ -2,94 +2,45 @@
 // head_kernel in s3r_pointwise.hip): x (B,C,S), w (C), scale one float or NULL, y and grad_y (B,S), act none / ReLU / sigmoid.  Three
 // results, each optional, each with a FIXED order — no atomics, the same bits on every run and at every 4-byte-aligned address:
 //
-//   g (B,S), the pre-activation gradient, fp32, nothing fused — s3r_linear_backward's rule:
-//       none: g = grad_y        ReLU: g = (y > 0.f) ? grad_y : 0.f  (a NaN y gives 0)        sigmoid: t = 1 - y; u = y * t; g = grad_y * u
+//   g (B,S), the pre-activation gradient, fp32, nothing fused: act_grad (s3r_ordered.h)
 //   gs = g * scale, rounded once (g itself when scale is NULL)
 //   grad_x[b][c][s] = gs[b][s] * w[c]            one multiplication
 //   grad_w[c]       = sum_{b,s} gs[b][s] x[b][c][s]
 //   grad_shift      = sum_{b,s} g[b][s]
 //
-// head_bwd_kernel streams the tensors once.  A WAVE owns one chunk of 512 consecutive positions of one sample: lane L (0..63) owns the
-// eight positions 256 j + 4 L + i (j = 0, 1; i = 0..3), i.e. two 16-byte loads per lane and tensor, 1 KiB contiguous per wave
-// instruction.  g and gs of the lane's positions are computed once and kept in registers; then the wave walks ALL C channels of
-// its positions — one read of x serves every channel sum — four channels' loads (8 per lane) in flight at a time:
+// The order of every sum is s3r_ordered.h's, a row being one sample's S positions.  head_bwd_kernel streams the tensors once: a WAVE owns
+// one chunk of one sample.  g and gs of the lane's eight positions are computed once and kept in registers; then the wave walks ALL C
+// channels of its positions — one read of x serves every channel sum — four channels' loads (8 per lane) in flight at a time:
 //   - grad_x: 16-byte stores of gs * w[c];
-//   - grad_w: the lane's partial starts as +0.0 and takes partial = partial + gs * x over its eight positions in ascending position
-//     (the product is rounded, then the add: NOT fused — a numpy restatement is then exact, and the kernel has VALU time to
-//     spare); the 64 partials are combined by the halving tree v[L] = v[L] + v[L + o] for L < o, o = 32, 16, 8, 4, 2, 1; lane 0
-//     stores the chunk sum to scratch[c][b][chunk];
+//   - grad_w: the lane's partial takes partial = partial + gs * x over its positions (the product is rounded, then the add: NOT fused — a
+//     numpy restatement is then exact, and the kernel has VALU time to spare); the chunk sum goes to scratch[c][b][chunk];
 //   - grad_shift: the same with plain adds of g, stored to scratch[C][b][chunk].
-// Positions past S contribute +0.0 (gs and x are both replaced by 0: 0 * NaN would be NaN), which changes no bit: a partial that
-// starts as +0.0 never holds -0.0, so partial + (+0.0) == partial.  The accesses go through a dword-aligned 16-byte vector type: a
-// pointer (or a row, when S is no multiple of 4) that is only 4-byte aligned runs the same instructions, and a chunk that crosses the
-// end of its row is read and written element by element (a wave-uniform choice) — the same arithmetic, the same bits.
-// A wave holds no channel state between channels, so C is unbounded, and there is no LDS and no barrier: waves are independent.
+// Positions past S contribute +0.0 (gs and x are both replaced by 0: 0 * NaN would be NaN).  A wave holds no channel state between
+// channels, so C is unbounded.
 //
-// head_bwd_finish_kernel: one wave per channel (and one for grad_shift).  Lane L sums the chunk sums of sample b0 + L in ascending
-// chunk order into a partial that starts as chunk 0's sum (a function of S only); the per-sample partials are then added into ONE
-// accumulator in ascending b, starting from sample 0's (lane by lane through a broadcast: every lane computes the same sum).
+// head_bwd_finish_kernel: one wave per channel (and one for grad_shift): row_total's sum of its row of scratch, written out in the kernel.
 //
 // Templates: GW / GX switch the x loads and the grad_x stores off entirely — grad_x NULL does not cost its write, grad_w NULL does
 // not cost the read of x; with neither, the channel loop is gone (grad_shift alone reads y and grad_y only).
-#include "s3r_kernels.h"
+#include "s3r_ordered.h"
 
 namespace s3r {
 
-typedef float v4f_h __attribute__((ext_vector_type(4)));
-typedef float v4f_hu __attribute__((ext_vector_type(4), aligned(4)));      // dword-aligned 16-byte access
-
-constexpr int HB_CHUNK = 512;        // positions per wave: 2 x (64 lanes x 16 bytes)
-constexpr int HB_Q = HB_CHUNK / 256; // 16-byte quads per lane
 constexpr int HB_UC = 4;             // channels whose loads are in flight together
-
-// positions i .. i + 3 of a row of n; `full` (wave-uniform: the wave's whole chunk lies inside the row) takes the 16-byte access, a
-// chunk that crosses the row's end goes element by element in every lane — no per-lane branch in the streaming path
-__device__ __forceinline__ v4f_h hb_load4(const float* __restrict__ p, long long i, long long n, bool full) {
-    if (full) return *reinterpret_cast<const v4f_hu*>(p + i);
-    v4f_h v;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = i + k < n ? p[i + k] : 0.f;
-    return v;
-}
-
-__device__ __forceinline__ void hb_store4(float* __restrict__ p, long long i, long long n, v4f_h v, bool full) {
-    if (full) { *reinterpret_cast<v4f_hu*>(p + i) = v; return; }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (i + k < n) p[i + k] = v[k];
-}
-
-__device__ __forceinline__ float hb_g(float y, float gy, int act) {
-#pragma clang fp contract(off)
-    if (act == 1) return (y > 0.f) ? gy : 0.f;
-    if (act == 2) {
-        const float t = 1.f - y;
-        const float u = y * t;
-        return gy * u;
-    }
-    return gy;
-}
-
-__device__ __forceinline__ float hb_tree(float v) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_down(v, o, 64);
-    return v;                                                            // (lane 0 holds the tree's root)
-}
 
 // channels c0 .. c0 + N - 1 (all < C) of one wave's chunk: the N channels' loads first, then per channel the stores and the chunk sum
 template <bool GW, bool GX, int N, bool FULL>
 __device__ __forceinline__ void hb_channels(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ gx,
-                                            float* __restrict__ part, const float (&gs)[HB_Q][4], int B, int C, long long S,
+                                            float* __restrict__ part, const float (&gs)[Q][4], int B, int C, long long S,
                                             long long nch, long long b, long long k, long long s0, int c0, int lane) {
 #pragma clang fp contract(off)
-    v4f_h xv[N][HB_Q];
+    v4f xv[N][Q];
     if (GW) {
 #pragma unroll
         for (int u = 0; u < N; ++u) {
             const float* __restrict__ xr = x + ((size_t)b * C + c0 + u) * S;
 #pragma unroll
-            for (int j = 0; j < HB_Q; ++j) xv[u][j] = hb_load4(xr, s0 + 256 * j, S, FULL);
+            for (int j = 0; j < Q; ++j) xv[u][j] = load4(xr, s0 + 256 * j, S, FULL);
         }
     }
 #pragma unroll
@@ -99,20 +50,20 @@ __device__ __forceinline__ void hb_channels(const float* __restrict__ x, const f
             const float wc = w[c];
             float* __restrict__ gr = gx + ((size_t)b * C + c) * S;
 #pragma unroll
-            for (int j = 0; j < HB_Q; ++j) {
-                v4f_h o;
+            for (int j = 0; j < Q; ++j) {
+                v4f o;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] = gs[j][i] * wc;
-                hb_store4(gr, s0 + 256 * j, S, o, FULL);
+                store4(gr, s0 + 256 * j, S, o, FULL);
             }
         }
         if (GW) {
             float a = 0.f;
 #pragma unroll
-            for (int j = 0; j < HB_Q; ++j)
+            for (int j = 0; j < Q; ++j)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) a = a + gs[j][i] * xv[u][j][i];
-            a = hb_tree(a);
+            a = wave_tree(a);
             if (lane == 0) part[((size_t)c * B + b) * nch + k] = a;
         }
     }
@@ -129,23 +80,23 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     const long long wid = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wid >= (long long)B * nch) return;                               // (wave-uniform; the kernel has no barrier)
     const long long b = wid / nch, k = wid - b * nch;
-    const long long s0 = k * HB_CHUNK + 4 * lane;
-    const bool full = (k + 1) * HB_CHUNK <= S;                           // (wave-uniform)
+    const long long s0 = k * CHUNK + 4 * lane;
+    const bool full = (k + 1) * CHUNK <= S;                           // (wave-uniform)
     const float sc = scale ? scale[0] : 1.f;
-    float g[HB_Q][4], gs[HB_Q][4];
+    float g[Q][4], gs[Q][4];
     {
-        v4f_h gv[HB_Q], yv[HB_Q];
+        v4f gv[Q], yv[Q];
 #pragma unroll
-        for (int j = 0; j < HB_Q; ++j) {
-            gv[j] = hb_load4(gy + (size_t)b * S, s0 + 256 * j, S, full);
-            yv[j] = act ? hb_load4(y + (size_t)b * S, s0 + 256 * j, S, full) : v4f_h{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < Q; ++j) {
+            gv[j] = load4(gy + (size_t)b * S, s0 + 256 * j, S, full);
+            yv[j] = act ? load4(y + (size_t)b * S, s0 + 256 * j, S, full) : v4f{0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
-        for (int j = 0; j < HB_Q; ++j)
+        for (int j = 0; j < Q; ++j)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const bool in = s0 + 256 * j + i < S;
-                const float v = hb_g(yv[j][i], gv[j][i], act);
+                const float v = act_grad(yv[j][i], gv[j][i], act);
                 g[j][i] = in ? v : 0.f;
                 gs[j][i] = in ? (scale ? v * sc : v) : 0.f;
             }
@@ -153,10 +104,10 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     if (shift) {
         float a = 0.f;
 #pragma unroll
-        for (int j = 0; j < HB_Q; ++j)
+        for (int j = 0; j < Q; ++j)
 #pragma unroll
             for (int i = 0; i < 4; ++i) a = a + g[j][i];
-        a = hb_tree(a);
+        a = wave_tree(a);
         if (lane == 0) part[((size_t)C * B + b) * nch + k] = a;
     }
     if (!GW && !GX) return;
@@ -176,6 +127,7 @@ __global__ __launch_bounds__(64) void head_bwd_finish_kernel(const float* __rest
     const int c = blockIdx.x, lane = threadIdx.x;
     float* __restrict__ dst = c < C ? (gw ? gw + c : nullptr) : gshift;
     if (!dst) return;
+    // row_total (s3r_ordered.h) with the row's base folded into each sample's address: the call itself measured 0.3 us slower (4.7 -> 5.0)
     float acc = 0.f;
     for (int b0 = 0; b0 < B; b0 += 64) {
         const int b = b0 + lane;
@@ -202,15 +154,13 @@ __global__ __launch_bounds__(64) void head_bwd_finish_kernel(const float* __rest
     if (lane == 0) *dst = acc;
 }
 
-static long long hb_chunks(int64_t S) { return ((long long)S + HB_CHUNK - 1) / HB_CHUNK; }
-
 // [C + 1][B][ceil(S / 512)] chunk sums: the worst case over the outputs, a function of the shape only, monotone in B
-int64_t head_backward_scratch_elems(int B, int C, int64_t S) { return ((int64_t)C + 1) * B * hb_chunks(S); }
+int64_t head_backward_scratch_elems(int B, int C, int64_t S) { return ((int64_t)C + 1) * B * chunks(S); }
 
 hipError_t launch_head_backward(const float* x, const float* w, const float* scale, const float* y, const float* gy, float* gx,
                                 float* gw, float* gshift, int B, int C, int64_t S, int act, float* scratch, hipStream_t s,
                                 int* launches) {
-    const long long nch = hb_chunks(S);
+    const long long nch = chunks(S);
     const dim3 grid((unsigned)(((long long)B * nch + 3) / 4));
     const int shift = gshift != nullptr;
 #define S3R_HB_LAUNCH(GW, GX) \

@@ -286,14 +286,14 @@ int64_t linear_scratch_elems(int B, int Cin, int Cout);
 hipError_t launch_linear_backward(const float* x, const float* w, const float* y, const float* gy, float* gx, float* gw, float* gb,
                                   int B, int Cin, int Cout, int act, float* scratch, hipStream_t s, int* launches);
 int64_t linear_backward_scratch_elems(int B, int Cin, int Cout);
-// s3r_head_bwd.hip: backward of the pointwise head y = act(fmaf(sum_c x w, scale, shift)), fixed summation orders, no atomics.  gx, gw,
+// s3r_head_bwd.hip: backward of the pointwise head y = act(fmaf(sum_c x w, scale, shift)), fixed summation orders (s3r_ordered.h), no atomics.  gx, gw,
 // gshift: NULL = not computed (not all three); scratch: head_backward_scratch_elems floats of chunk sums
 hipError_t launch_head_backward(const float* x, const float* w, const float* scale, const float* y, const float* gy, float* gx,
                                 float* gw, float* gshift, int B, int C, int64_t S, int act, float* scratch, hipStream_t s,
                                 int* launches);
 int64_t head_backward_scratch_elems(int B, int C, int64_t S);
 // s3r_batchnorm.hip: train-mode BatchNorm on z (B,C,S) with batch statistics: two-pass mean / biased variance, y = act(xhat * gamma + beta),
-// and its backward; fixed summation orders (the head backward's, a (b, c) row in place of a sample), no atomics.  gz, ggamma, gbeta: NULL =
+// and its backward; fixed summation orders (s3r_ordered.h's, a row being one (b, c)), no atomics.  gz, ggamma, gbeta: NULL =
 // not computed (not all three); scratch: batchnorm_{forward,backward}_scratch_elems floats of chunk sums
 hipError_t launch_batchnorm_train_forward(const float* z, const float* gamma, const float* beta, float eps, int act, float* y,
                                           float* mean, float* var, float* invstd, int B, int C, int64_t S, float* scratch, hipStream_t s,
@@ -304,7 +304,7 @@ hipError_t launch_batchnorm_train_backward(const float* z, const float* y, const
 int64_t batchnorm_forward_scratch_elems(int B, int C, int64_t S);
 int64_t batchnorm_backward_scratch_elems(int B, int C, int64_t S);
 // s3r_conv_bwd.hip: backward of one fp32 Conv / ConvTranspose layer except its input gradient (that is the adjoint layer's forward):
-// gs = g * scale, grad_shift in the head backward's order, grad_w as a sliced GEMM whose slabs are added in a fixed order.
+// gs = g * scale, grad_shift in s3r_ordered.h's order, grad_w as a sliced GEMM whose slabs are added in a fixed order.
 // ConvBwdGeo: the weight-gradient GEMM's tiling, a function of the layer's per-sample geometry only (convbwd_geo; false: no tiling fits)
 struct ConvBwdGeo {
     int nd, k, s, p;
@@ -326,8 +326,9 @@ int64_t conv_backward_scratch_elems(const ConvBwdGeo& g, int B, int cout, int64_
 hipError_t launch_conv_backward(const ConvBwdGeo& g, int deconv, const float* x, const float* y, const float* gy, const float* scale,
                                 float* gs, float* gw, float* gshift, int B, int cout, int64_t S, int act, float* scratch, hipStream_t s,
                                 int* launches);
-hipError_t launch_convbwd_shift(const float* y, const float* gy, int B, int cout, int64_t S, int act, float* part, float* gshift,
-                                hipStream_t s, int* launches);
+// the prep pass and grad_shift's row totals on their own (gs, gshift: NULL = not computed; part: cout B ceil(S / 512) floats, used with gshift)
+hipError_t launch_convbwd_prep(const float* y, const float* gy, const float* scale, float* gs, float* gshift, int B, int cout, int64_t S,
+                               int act, float* part, hipStream_t s, int* launches);
 // s3r_stem_bwd.hip: grad_w and grad_shift of the stem (conv2d 3 -> 32, k 3, s 2, p 1) from fp32 or 8-bit renders in one or two tensors;
 // one wave per K slice of stem_bwd_rows(m) output rows, slabs added per image, then over the images, in ascending order
 int stem_bwd_rows(int m);

@@ -3,8 +3,7 @@
 // the same bits on every run and at every 4-byte-aligned address (every access below is one dword per lane: nothing depends on
 // a wider alignment, so there is no second code path an address could select):
 //
-//   g (B,Cout), the pre-activation gradient, fp32, nothing fused (contraction off):
-//       none: g = grad_y        ReLU: g = (y > 0.f) ? grad_y : 0.f  (a NaN y gives 0)        sigmoid: t = 1 - y; u = y * t; g = grad_y * u
+//   g (B,Cout), the pre-activation gradient, fp32, nothing fused (contraction off): act_grad (s3r_ordered.h)
 //   grad_bias[o] = sum_b g[b][o]          one accumulator that starts as g[0][o], plain adds in ascending b   (linbwd_prep_kernel)
 //   grad_w[o][i] = sum_b g[b][o] x[b][i]  a GEMM with M = Cout, N = Cin, K = B                                 (linbwd_gw_kernel)
 //   grad_x[b][i] = sum_o g[b][o] w[o][i]  a GEMM with M = B, N = Cin, K = Cout                                 (linbwd_gx_kernel)
@@ -37,22 +36,11 @@
 // products to an accumulator that started as +0.0, which changes no bit: under round-to-nearest a sum is -0.0 only when BOTH addends
 // are -0.0, so an accumulator that starts as +0.0 never holds -0.0 and acc + (+0.0) == acc bit for bit.  All indexing is 64-bit element arithmetic on plain
 // pointers; the grids are one-dimensional (no 65535 limit on a tile count).
-#include "s3r_kernels.h"
+#include "s3r_ordered.h"
 
 namespace s3r {
 
 typedef float f32x16_b __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float linbwd_g(float y, float gy, int act) {
-#pragma clang fp contract(off)
-    if (act == 1) return (y > 0.f) ? gy : 0.f;
-    if (act == 2) {
-        const float t = 1.f - y;
-        const float u = y * t;
-        return gy * u;
-    }
-    return gy;
-}
 
 // one thread per o; b ascending; g stored when gbuf != NULL, the bias sum when gbias != NULL.  y is NULL when act is none
 __global__ __launch_bounds__(64) void linbwd_prep_kernel(const float* __restrict__ y, const float* __restrict__ gy,
@@ -73,14 +61,14 @@ __global__ __launch_bounds__(64) void linbwd_prep_kernel(const float* __restrict
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            const float g = linbwd_g(yy[u], v[u], act);
+            const float g = act_grad(yy[u], v[u], act);
             if (gbuf) gbuf[(size_t)(b + u) * Cout + o] = g;
             s = (b + u == 0) ? g : s + g;
         }
     }
     for (; b < B; ++b) {
         const size_t at = (size_t)b * Cout + o;
-        const float g = linbwd_g(act ? y[at] : 0.f, gy[at], act);
+        const float g = act_grad(act ? y[at] : 0.f, gy[at], act);
         if (gbuf) gbuf[at] = g;
         s = (b == 0) ? g : s + g;
     }

@@ -5,7 +5,7 @@
 //
 //   g, gs         s3r_conv_backward's rule:  none: g = grad_y;  ReLU: g = (y > 0.f) ? grad_y : 0.f;  gs = g * scale[o] rounded once
 //   grad_shift[o] = sum g: the conv backward's OWN two kernels (convbwd_prep_kernel without a gs output + convbwd_shift_finish_kernel,
-//                   launch_convbwd_shift) over (image, channel) rows of S = m^2 positions: the same code, hence the same bits.  A pass
+//                   launch_convbwd_prep) over (image, channel) rows of S = m^2 positions: the same code, hence the same bits.  A pass
 //                   of its own over grad_y and y: the chunks of 512 flat positions it sums do not line up with the output rows the
 //                   weight-gradient kernel walks.
 //   grad_w[o][ci][kh][kw] = sum_{image, oh, ow} gs[image][o][oh][ow] X[image][ci][2 oh - 1 + kh][2 ow - 1 + kw]   (X is 0 outside the image)
@@ -26,26 +26,21 @@
 // stem_bwd_image_kernel: per element, an image's slabs in ascending slice order starting from slab 0 (skipped when an image is one slice).
 // stem_bwd_batch_kernel: per element, the images' partials in ascending image index starting from image 0's (skipped for one image).
 // An image's partial is therefore a function of in_size and its own data only.  64-bit element arithmetic; one-dimensional grids.
-#include "s3r_kernels.h"
+#include "s3r_ordered.h"
 
 namespace s3r {
 
 typedef float f32x16_s __attribute__((ext_vector_type(16)));
-typedef float v4f_s __attribute__((ext_vector_type(4)));
-typedef float v4f_su __attribute__((ext_vector_type(4), aligned(4)));      // dword-aligned 16-byte access
-
 constexpr int SB_CO = 32;                      // output channels: the M tile
 constexpr int SB_TAPS = 27;                    // 3 x 3 x 3 taps: the live columns of the N tile
 constexpr int SB_RUN = 64;                     // positions per staged segment
 constexpr int SB_ASTR = SB_RUN + 1;            // 65
 constexpr int SB_XSTR = 131;                   // >= the 2 * SB_RUN + 1 = 129 input columns that serve 64 positions x 3 taps at stride 2, and = 3 mod 32
 constexpr int SB_SLAB = SB_CO * SB_TAPS;       // 864
-constexpr int SB_CHUNK = 512;                  // the shift sums' chunk (s3r_conv_bwd.hip)
 
 // output rows per K slice: a function of m alone; at most 32 slices per image
 int stem_bwd_rows(int m) { return (m + 31) / 32; }
 static int sb_slices(int m) { const int rps = stem_bwd_rows(m); return (m + rps - 1) / rps; }
-static long long sb_chunks(long long S) { return (S + SB_CHUNK - 1) / SB_CHUNK; }
 
 template <typename TI>
 __global__ __launch_bounds__(64, 3) void stem_bwd_gw_kernel(const TI* __restrict__ left, const TI* __restrict__ right, int n_left,
@@ -79,14 +74,14 @@ __global__ __launch_bounds__(64, 3) void stem_bwd_gw_kernel(const TI* __restrict
         for (int w0 = 0; w0 < m; w0 += SB_RUN) {
             const int len = min(SB_RUN, m - w0);
             // -- global loads of the segment: gs operands, then the nine input rows
-            v4f_s gv[8], yv[8];
+            v4f gv[8], yv[8];
             const bool quad = w0 + q4 + 3 < m;
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const size_t row = (size_t)(4 * u + cq) * S + (size_t)oh * m;
                 if (quad) {
-                    gv[u] = *reinterpret_cast<const v4f_su*>(gyb + row + w0 + q4);
-                    yv[u] = act ? *reinterpret_cast<const v4f_su*>(yb + row + w0 + q4) : v4f_s{0.f, 0.f, 0.f, 0.f};
+                    gv[u] = *reinterpret_cast<const v4f_u*>(gyb + row + w0 + q4);
+                    yv[u] = act ? *reinterpret_cast<const v4f_u*>(yb + row + w0 + q4) : v4f{0.f, 0.f, 0.f, 0.f};
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -120,7 +115,7 @@ __global__ __launch_bounds__(64, 3) void stem_bwd_gw_kernel(const TI* __restrict
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const bool ok = w0 + q4 + i < m;
-                    const float g = act == 1 ? ((yv[u][i] > 0.f) ? gv[u][i] : 0.f) : gv[u][i];
+                    const float g = act == 1 ? ((yv[u][i] > 0.f) ? gv[u][i] : 0.f) : gv[u][i];      // (act_grad's none / ReLU, s3r_ordered.h)
                     const float gs = scale ? g * scv[u] : g;
                     dst[i] = ok ? gs : 0.f;
                 }
@@ -188,7 +183,7 @@ __global__ __launch_bounds__(256) void stem_bwd_batch_kernel(const float* __rest
 int64_t stem_backward_scratch_elems(int B, int m) {
     if (B <= 0) return 0;
     const long long S = (long long)m * m;
-    return (int64_t)SB_CO * B * sb_chunks(S) + (int64_t)B * sb_slices(m) * SB_SLAB + (int64_t)B * SB_SLAB;
+    return (int64_t)SB_CO * B * chunks(S) + (int64_t)B * sb_slices(m) * SB_SLAB + (int64_t)B * SB_SLAB;
 }
 
 hipError_t launch_stem_backward(const void* left, const void* right, int n_left, int u8, const float* y, const float* gy,
@@ -198,10 +193,10 @@ hipError_t launch_stem_backward(const void* left, const void* right, int n_left,
     const long long S = (long long)m * m;
     const int nsl = sb_slices(m), rps = stem_bwd_rows(m);
     float* part = scratch;
-    float* slabs = part + (size_t)SB_CO * B * sb_chunks(S);
+    float* slabs = part + (size_t)SB_CO * B * chunks(S);
     float* imgs = slabs + (size_t)B * nsl * SB_SLAB;
     if (gshift) {
-        hipError_t e = launch_convbwd_shift(y, gy, B, SB_CO, S, act, part, gshift, s, launches);
+        hipError_t e = launch_convbwd_prep(y, gy, nullptr, nullptr, gshift, B, SB_CO, S, act, part, s, launches);
         if (e != hipSuccess) return e;
     }
     if (gw) {

@@ -21,27 +21,25 @@
 //
 // grad_pred (voxel_bce_bwd_kernel, elementwise over the flat (B V) tensor):
 //   n = grad_scale[b] * (p - t);  d = max((1.f - p) * p, 1e-12f);  grad_pred = n / d    (IEEE division)
-#include "s3r_kernels.h"
+#include "s3r_ordered.h"
 
 namespace s3r {
-
-typedef float v4f_l __attribute__((ext_vector_type(4)));
-typedef float v4f_lu __attribute__((ext_vector_type(4), aligned(4)));      // dword-aligned 16-byte access
 
 constexpr int BCE_CHUNK = 1024;      // elements per chunk: 4 x (64 lanes x 16 bytes)
 constexpr int BCE_WAVES = 16;        // waves per workgroup = chunks per round
 
+// not s3r_ordered.h's load4 / store4: the choice is per quad, with a fill value, in chunks of 1024
 // elements i .. i + 3 of a tensor of n elements; `fill` where i + k >= n (never read)
-__device__ __forceinline__ v4f_l bce_load4(const float* __restrict__ p, long long i, long long n, float fill) {
-    if (i + 4 <= n) return *reinterpret_cast<const v4f_lu*>(p + i);
-    v4f_l v;
+__device__ __forceinline__ v4f bce_load4(const float* __restrict__ p, long long i, long long n, float fill) {
+    if (i + 4 <= n) return *reinterpret_cast<const v4f_u*>(p + i);
+    v4f v;
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = i + k < n ? p[i + k] : fill;
     return v;
 }
 
-__device__ __forceinline__ void bce_store4(float* __restrict__ p, long long i, long long n, v4f_l v) {
-    if (i + 4 <= n) { *reinterpret_cast<v4f_lu*>(p + i) = v; return; }
+__device__ __forceinline__ void bce_store4(float* __restrict__ p, long long i, long long n, v4f v) {
+    if (i + 4 <= n) { *reinterpret_cast<v4f_u*>(p + i) = v; return; }
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if (i + k < n) p[i + k] = v[k];
@@ -73,7 +71,7 @@ __global__ __launch_bounds__(64 * BCE_WAVES) void voxel_bce_kernel(const float* 
         const long long ch = c0 + wave;
         float s = 0.f;
         if (ch < nch) {                                                  // (wave-uniform)
-            v4f_l pv[4], tv[4];
+            v4f pv[4], tv[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {                                // all eight loads in flight before the first logf
                 const long long e = ch * BCE_CHUNK + 256 * j + 4 * lane;
@@ -83,7 +81,7 @@ __global__ __launch_bounds__(64 * BCE_WAVES) void voxel_bce_kernel(const float* 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long long e = ch * BCE_CHUNK + 256 * j + 4 * lane;
-                v4f_l l;
+                v4f l;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     l[i] = bce_elem(pv[j][i], tv[j][i]);
@@ -91,8 +89,7 @@ __global__ __launch_bounds__(64 * BCE_WAVES) void voxel_bce_kernel(const float* 
                 }
                 if (le) bce_store4(le, e, V, l);
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s = s + __shfl_down(s, o, 64);      // lane 0: the halving tree
+            s = wave_tree(s);
         }
         if (lane == 0) csum[wave] = s;
         __syncthreads();
@@ -113,8 +110,8 @@ __global__ __launch_bounds__(256) void voxel_bce_bwd_kernel(const float* __restr
     const long long i0 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i0 >= total) return;
     long long b = i0 / V, r = i0 - b * V;
-    const v4f_l p = bce_load4(pred, i0, total, 0.5f), t = bce_load4(target, i0, total, 0.5f);
-    v4f_l g;
+    const v4f p = bce_load4(pred, i0, total, 0.5f), t = bce_load4(target, i0, total, 0.5f);
+    v4f g;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         g[k] = 0.f;
