@@ -41,6 +41,10 @@
  *                                           ground truth's render resolution, with a confidence map   (README.md:75-76)
  *   s3r_disparity_metrics                   the end-point error and bad-pixel rates (>1 px, >3 px, KITTI D1) of a
  *                                           stereo evaluation against those maps        (README.md:75-76)
+ *   s3r_disparity_soft_backward             torch autograd's backward of that read-out (abs, softmax, bilinear upsample) down to the two
+ *                                           feature maps: what `python3 runner.py` runs behind a disparity loss (README.md:75-76)
+ *   s3r_disparity_loss_forward / _backward  torch.nn.SmoothL1Loss on the pixels with a valid ground truth (the disp_%02d_{l,r}.exr maps
+ *                                           mark background as inf or negative) and its backward, fixed summation order (README.md:75-76)
  *
  * Conventions
  *   - every tensor is fp32, contiguous, NCHW / NCDHW, resident in device memory owned by the caller;
@@ -81,7 +85,8 @@ extern "C" {
  * the version stays 8.  s3r_chamfer_backward and s3r_linear_backward (+ its scratch query) likewise; s3r_voxel_bce_forward,
  * s3r_voxel_bce_backward and s3r_head_backward (+ its scratch query) likewise; s3r_conv_adjoint_desc and s3r_conv_backward (+ its scratch
  * query) likewise; s3r_cost_volume_backward likewise; s3r_batchnorm_train_forward and s3r_batchnorm_train_backward (+ their scratch queries)
- * likewise; s3r_stem_backward (+ its scratch query) likewise: new entry points only, the version stays 8. */
+ * likewise; s3r_stem_backward (+ its scratch query) likewise; s3r_disparity_soft_backward, s3r_disparity_loss_forward and
+ * s3r_disparity_loss_backward likewise: new entry points only, the version stays 8. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -695,9 +700,96 @@ int s3r_disparity_soft(const void* feat_l, const void* feat_r, int feat_dtype, f
 int s3r_disparity_metrics(const float* pred, const float* gt, float* epe, int32_t* counts, int batch, int64_t pixels,
                           void* stream);
 
+/* Backward of s3r_disparity_soft: the gradient of  sum grad_disp_l * disp_l + sum grad_disp_r * disp_r  with respect to the two feature
+ * maps.  feat_l, feat_r (B,C,H,W) fp32 (feat_dtype S3R_F32; S3R_BF16 is S3R_ERR_INVALID: no bf16 backward exists in the library);
+ * grad_disp_l, grad_disp_r (B,OH,OW) fp32, the gradients of the two disparity maps; grad_left, grad_right (B,C,H,W).  max_disp,
+ * temperature, out_height, out_width and disp_scale as in the forward call that produced the maps.  Nothing is saved by the forward: the
+ * costs c(d), their minimum, the weights e_d (with the subnormal rule), Z, S and disp = S / Z are recomputed with the forward's operations
+ * in the forward's order (ascending d; Z = Z + e_d, S = S + (float)d * e_d, the product rounded before the add).  The confidence maps get no
+ * gradient, and there is no gradient with respect to the temperature.
+ * All arithmetic is fp32, every operation rounded once, nothing contracted.  Per sample, direction X in {L, R} and feature pixel (h, w):
+ *   G_X[h,w]  the feature-size gradient.  At out_height == H and out_width == W:  G = grad_disp_X[h,w] * disp_scale.  Otherwise the adjoint
+ *             of the forward's bilinear blend, with the forward's source rule (i0, i1, lam)(o) = bilinear source of output index o (src =
+ *             (o + 0.5) in / out - 0.5 clamped at 0, in / out one fp32 division, i0 = (int)src clamped at in - 1, i1 = i0 + 1 clamped at
+ *             in - 1, lam = src - i0) and the weight with which output index o reads source index i
+ *                 wt(o, i) = (i0 == i ? 1.f - lam : 0.f) + (i1 == i ? lam : 0.f)            (an edge-clamped i0 == i1 contributes both)
+ *             gathered over the output pixels that read (h, w) — the rows oy with i0(oy) in {h - 1, h} and the columns ox with i0(ox) in
+ *             {w - 1, w}, one contiguous window each — rows ascending, columns ascending within a row, into ONE accumulator that starts
+ *             as +0.0:
+ *                 acc = acc + ((grad_disp_X[oy,ox] * disp_scale) * wt(oy, h)) * wt(ox, w)
+ *             A feature pixel that no output pixel reads (a downsample) has G = +0.0.  A NULL grad_disp_X is a tensor of zeros: G = +0.0.
+ *   k = G / temperature;  p_d = e_d / Z;  t_d = p_d * (disp - (float)d);  q^X_d(h,w) = t_d * k          (IEEE divisions)
+ *             (subtracting the minimum is a shift of the softmax: no term; a weight the subnormal rule flushed to 0 has p_d = 0 and q = 0)
+ * and with n_L(w) = min(max_disp, w + 1), n_R(w) = min(max_disp, W - w):
+ *   grad_left [b,c,h,w] = sum_{d = 0 .. n_L(w)-1} sgn(L[c,h,w] - R[c,h,w-d]) * (q^L_d(h,w) + q^R_d(h,w-d))
+ *   grad_right[b,c,h,w] = sum_{d = 0 .. n_R(w)-1} sgn(R[c,h,w] - L[c,h,w+d]) * (q^R_d(h,w) + q^L_d(h,w+d))
+ * Order, which IS the contract: per output element and per d the inner sum u_d is ONE add (the own direction's q first); the term is
+ * (a > m) ? u_d : ((a < m) ? -u_d : 0.f) for the own feature a and the matched feature m — u_d, its negation, or 0 where the two are equal
+ * (torch's abs backward; two features that do not compare, a NaN, give 0 as well); the accumulator starts AS the d = 0 term (not as +0.0)
+ * and takes the others one at a time in ascending d.  Every output is its own sequential sum: no atomics, no cross-lane reduction, no
+ * scratch — the same bits on every run, at every address and in every batch a sample appears in.  The sign of a zero is not part of the
+ * contract.  expf is the device math library's, as in the forward (not correctly rounded: the values are not a bit-for-bit contract
+ * against a restatement unless every cost of a pixel is equal — then every weight is expf(0) = 1 and all of the above is exact).
+ * NaN / Inf: a non-finite value propagates through exactly this arithmetic (0.f * NaN is NaN: an output pixel with lam = 0 still hands a
+ * NaN gradient to its upper neighbour, as the forward's blend hands it a NaN value); a NaN in a sample's grad_disp or features stays in
+ * that sample.
+ * grad_disp_l or grad_disp_r may be NULL (zeros, the same bits as a zero tensor); both NULL is S3R_ERR_INVALID.  grad_left or grad_right
+ * may be NULL: that output is not computed and the other keeps the bits of the full call; both NULL is S3R_ERR_INVALID.  Outputs are
+ * overwritten, never accumulated into.  Limits: the forward's, refused with the forward's messages — temperature finite and > 0, dims
+ * >= 1 (batch >= 0; 0 launches nothing and returns S3R_OK), LDS 4 (2 C W + 2 W min(max_disp, W) + 12 W) bytes within 64 KiB (this kernel
+ * needs 4 (2 C W + 2 W min(max_disp, W) + 2 W)), every tensor < 2^31 elements, batch x out_height < 2^24 — and batch x height < 2^24.
+ * 4-byte alignment for every argument.  Nothing is enqueued when the call is refused.  One kernel launch, one workgroup per (sample,
+ * feature row).
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new data in the same buffers).
+ * Profiler: ONE record of family 9, tag 4; `flops` = 0; `bytes` = the features read once, each gradient given read once, each output asked
+ * for written once: 4 (2 B C H W + [1 or 2] B OH OW + [1 or 2] B C H W). */
+int s3r_disparity_soft_backward(const void* feat_l, const void* feat_r, int feat_dtype, const float* grad_disp_l,
+                                const float* grad_disp_r, float* grad_left, float* grad_right, int batch, int channels, int height,
+                                int width, int max_disp, float temperature, int out_height, int out_width, float disp_scale,
+                                void* hip_stream);
+
+/* Smooth-L1 (Huber) loss of a disparity map against a ground truth with invalid pixels.  pred, gt (B, P) fp32; a pixel is VALID exactly as
+ * for s3r_disparity_metrics: its ground truth is finite and >= 0 (the EXR maps mark background as inf or a negative value; NaN is invalid).
+ * Per valid element, fp32, every operation rounded once, nothing contracted, with e = pred - gt and a = |e|:
+ *   a < beta:   h = 0.5f * e;  s = h * e;  l = s / beta           (IEEE division)
+ *   otherwise:  l = a - 0.5f * beta                                (beta == 0: l = |e|, plain L1; a == beta takes this branch)
+ * An invalid element counts as +0.0 by a SELECT: its pred and gt never enter arithmetic (not a multiplication by a mask: 0 * NaN is NaN),
+ * so a NaN or an infinity of pred at an invalid pixel changes no bit.  A NaN pred at a VALID pixel compares false, takes the second branch
+ * and gives a NaN l: it propagates through exactly this arithmetic into that sample's loss_sum — that sample only; it is not an error.
+ * loss_sum (B): the fp32 sum of the sample's P values in s3r_voxel_bce_forward's order, a function of P only — never of B, the device or
+ * an address: chunks of 1024 consecutive elements (the last may be short; missing elements count as +0.0); within a chunk lane L (0..63)
+ * owns the 16 elements 256 j + 4 L + i (j = 0..3, i = 0..3) and adds them in ascending element order to a partial that starts as +0.0;
+ * the 64 partials are combined by the halving tree v[L] = v[L] + v[L + o] for L < o, o = 32, 16, 8, 4, 2, 1; the chunk sums are added in
+ * ascending chunk order into one accumulator that starts as chunk 0's sum.  count (B) int32: the sample's valid pixels, exact.
+ * loss_elem (B, P) may be NULL; otherwise it receives every l (+0.0 at invalid pixels), and passing it changes no bit of loss_sum.
+ * pred, gt, loss_sum and count non-NULL.  beta finite and >= 0; batch >= 0 (0 launches nothing and returns S3R_OK); pixels > 0; the
+ * tensors < 2^31 elements and < 4 GiB; 4-byte alignment for every argument, the same bits at every address.  Outputs are overwritten.
+ * Nothing is enqueued when the call is refused.  One kernel launch, one workgroup per sample, no atomics, no scratch.
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new data in the same buffers).
+ * Profiler: ONE record of family 9, tag 5; `bytes` = pred, gt, loss_elem when given, loss_sum and count. */
+int s3r_disparity_loss_forward(const float* pred, const float* gt, float beta, float* loss_sum, int32_t* count, float* loss_elem,
+                               int batch, int64_t pixels, void* hip_stream);
+
+/* Gradient of sum_b grad_scale[b] * loss_sum[b] with respect to pred: grad_pred (B, P), grad_scale (B); for the mean over the valid pixels
+ * of the batch a caller passes grad_output / max(sum_b count[b], 1) in every grad_scale[b].  Per VALID element, fp32, each operation
+ * rounded once, with e = pred - gt:
+ *   beta > 0:   v = e / beta;  c = (v < -1.f) ? -1.f : ((v > 1.f) ? 1.f : v);  grad_pred = grad_scale[b] * c       (clamp(e / beta, -1, 1))
+ *   beta == 0:  c = (e > 0.f) ? 1.f : ((e < 0.f) ? -1.f : ((e == 0.f) ? 0.f : e));  grad_pred = grad_scale[b] * c   (sgn(e))
+ * and exactly +0.0 at an invalid element, by a select.  Elementwise: bit for bit against a restatement.  The clamp is two compare-and-
+ * selects, so a NaN pred at a valid pixel propagates through it into that element's gradient and no other.  All four pointers non-NULL;
+ * beta, dims, limits, alignment and batch == 0 as the forward.  Outputs are overwritten.  Nothing is enqueued when the call is refused.
+ * One kernel launch.
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new data in the same buffers).
+ * Profiler: ONE record of family 9, tag 6; `bytes` = pred, gt, grad_pred and grad_scale. */
+int s3r_disparity_loss_backward(const float* pred, const float* gt, const float* grad_scale, float beta, float* grad_pred, int batch,
+                                int64_t pixels, void* hip_stream);
+
 /* Kernel-level profiler: when enabled, every kernel the library launches is bracketed by HIP events
  * on the launch stream.  s3r_profile_read synchronises those events and returns, per launch, the
- * kernel family (0 mfma conv, 1 stem, 2 head (tag 1: its backward), 3 cost volume, 4 linear, 5 chamfer, 6 iou (tags 1, 2: voxel BCE), 7 pack, 8 pad copy, 9 disparity read-out / epe,
+ * kernel family (0 mfma conv, 1 stem, 2 head (tag 1: its backward), 3 cost volume, 4 linear, 5 chamfer, 6 iou (tags 1, 2: voxel BCE), 7 pack, 8 pad copy, 9 disparity read-out / epe (tag 4: the soft read-out's backward; 5, 6: the disparity loss),
  * 10 aux: ONE transform / difference / finish / split-K-combine pass of a convolution layer — no matrix work, `bytes` = what it must
  * read and write — recorded INSIDE that layer's family-0 record, same tag: the layer's record includes its aux passes' time),
  * the caller's tag, milliseconds, and the algorithmic flops / bytes of that launch. */

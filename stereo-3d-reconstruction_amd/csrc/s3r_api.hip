@@ -1314,18 +1314,17 @@ int s3r_disparity_epe(const float* pred, const float* gt, float* epe, int32_t* c
 // ---------------------------------------------------------------- sub-pixel read-out and stereo metrics (s3r_disparity.hip)
 extern "C" {
 
-int s3r_disparity_soft(const void* feat_l, const void* feat_r, int feat_dtype, float* disp_l, float* disp_r, float* conf_l,
-                       float* conf_r, int batch, int channels, int height, int width, int max_disp, float temperature,
-                       int out_height, int out_width, float disp_scale, void* stream) {
+// The soft read-out's argument checks, shared by the forward and its backward (one message path: what the forward refuses, the
+// backward refuses in the same words).  soft_args: temperature and dims; soft_shape: the LDS rule and the size limits.
+static int soft_args(int batch, int channels, int height, int width, int max_disp, float temperature, int out_height, int out_width) {
     if (!(temperature > 0.f) || !std::isfinite(temperature))
         return fail(S3R_ERR_INVALID, "soft read-out temperature must be finite and > 0 (got %g)", (double)temperature);
     if (batch < 0 || channels <= 0 || height <= 0 || width <= 0 || max_disp <= 0 || out_height <= 0 || out_width <= 0)
         return fail(S3R_ERR_INVALID, "soft read-out dims must be positive (batch >= 0)");
-    if (feat_dtype != S3R_F32 && feat_dtype != S3R_BF16) return fail(S3R_ERR_INVALID, "unknown feature dtype %d", feat_dtype);
-    const bool bf16 = feat_dtype == S3R_BF16;
-    if (bf16 && channels % 8 != 0) return fail(S3R_ERR_INVALID, "bf16 channels-last features need channels %% 8 == 0");
-    if (bf16 && batch > 0 && (((uintptr_t)feat_l | (uintptr_t)feat_r) & 15))
-        return fail(S3R_ERR_INVALID, "bf16 features must start 16-byte aligned (16-byte loads)");
+    return S3R_OK;
+}
+
+static int soft_shape(int batch, int channels, int height, int width, int max_disp, int out_height, int out_width) {
     if (s3r::disparity_soft_lds_bytes(channels, max_disp, width) > 64 * 1024)
         return fail(S3R_ERR_INVALID, "soft read-out: 4*(2*C*W + 2*W*min(max_disp, W) + 12*W) bytes must fit 64 KiB of LDS");
     const int64_t feat = (int64_t)batch * channels * height * width;
@@ -1333,6 +1332,23 @@ int s3r_disparity_soft(const void* feat_l, const void* feat_r, int feat_dtype, f
     if (feat >= kMaxElems || out >= kMaxElems) return fail(S3R_ERR_INVALID, "tensor of 2^31 elements or more: split the batch");
     if ((int64_t)batch * out_height >= (1 << 24))      // at most one workgroup of 256 per output row: < 2^32 work-items
         return fail(S3R_ERR_INVALID, "batch x out_height must stay below 2^24: split the batch");
+    return S3R_OK;
+}
+
+int s3r_disparity_soft(const void* feat_l, const void* feat_r, int feat_dtype, float* disp_l, float* disp_r, float* conf_l,
+                       float* conf_r, int batch, int channels, int height, int width, int max_disp, float temperature,
+                       int out_height, int out_width, float disp_scale, void* stream) {
+    int rc = soft_args(batch, channels, height, width, max_disp, temperature, out_height, out_width);
+    if (rc) return rc;
+    if (feat_dtype != S3R_F32 && feat_dtype != S3R_BF16) return fail(S3R_ERR_INVALID, "unknown feature dtype %d", feat_dtype);
+    const bool bf16 = feat_dtype == S3R_BF16;
+    if (bf16 && channels % 8 != 0) return fail(S3R_ERR_INVALID, "bf16 channels-last features need channels %% 8 == 0");
+    if (bf16 && batch > 0 && (((uintptr_t)feat_l | (uintptr_t)feat_r) & 15))
+        return fail(S3R_ERR_INVALID, "bf16 features must start 16-byte aligned (16-byte loads)");
+    rc = soft_shape(batch, channels, height, width, max_disp, out_height, out_width);
+    if (rc) return rc;
+    const int64_t feat = (int64_t)batch * channels * height * width;
+    const int64_t out = (int64_t)batch * out_height * out_width;
     if (batch == 0) return S3R_OK;
     if (!feat_l || !feat_r) return fail(S3R_ERR_INVALID, "null feature pointer");
     hipStream_t s = (hipStream_t)stream;
@@ -1356,6 +1372,75 @@ int s3r_disparity_metrics(const float* pred, const float* gt, float* epe, int32_
     ProfScope ps(s, F_DISP, 3, 0.0, 8.0 * batch * (double)pixels + 20.0 * batch);
     hipError_t e = s3r::launch_disparity_metrics(pred, gt, epe, counts, batch, pixels, s);
     if (e != hipSuccess) return hip_fail(e, "disparity metrics launch");
+    return S3R_OK;
+}
+
+// ---------------------------------------------------------------- disparity supervision (s3r_disparity_bwd.hip, s3r_disparity_loss.hip)
+int s3r_disparity_soft_backward(const void* feat_l, const void* feat_r, int feat_dtype, const float* grad_disp_l,
+                                const float* grad_disp_r, float* grad_left, float* grad_right, int batch, int channels, int height,
+                                int width, int max_disp, float temperature, int out_height, int out_width, float disp_scale,
+                                void* hip_stream) {
+    if (!grad_disp_l && !grad_disp_r)
+        return fail(S3R_ERR_INVALID, "soft read-out backward: grad_disp_l and grad_disp_r are both NULL (either may be: it counts as zeros)");
+    if (!grad_left && !grad_right)
+        return fail(S3R_ERR_INVALID, "soft read-out backward: grad_left and grad_right are both NULL (either may be: it is not computed)");
+    int rc = soft_args(batch, channels, height, width, max_disp, temperature, out_height, out_width);
+    if (rc) return rc;
+    if (feat_dtype == S3R_BF16)
+        return fail(S3R_ERR_INVALID, "soft read-out backward: bf16 features have no backward (fp32 NCHW features only)");
+    if (feat_dtype != S3R_F32) return fail(S3R_ERR_INVALID, "unknown feature dtype %d", feat_dtype);
+    rc = soft_shape(batch, channels, height, width, max_disp, out_height, out_width);
+    if (rc) return rc;
+    if ((int64_t)batch * height >= (1 << 24))          // one workgroup of 256 per feature row: < 2^32 work-items
+        return fail(S3R_ERR_INVALID, "batch x height must stay below 2^24: split the batch");
+    if (batch == 0) return S3R_OK;
+    if (!feat_l || !feat_r) return fail(S3R_ERR_INVALID, "null feature pointer");
+    hipStream_t s = (hipStream_t)hip_stream;
+    const double feat = (double)batch * channels * height * width;
+    const double out = (double)batch * out_height * out_width;
+    const int grads = !!grad_disp_l + !!grad_disp_r, outs = !!grad_left + !!grad_right;
+    ProfScope ps(s, F_DISP, 4, 0.0, 4.0 * (2.0 * feat + grads * out + outs * feat));
+    hipError_t e = s3r::launch_disparity_soft_backward((const float*)feat_l, (const float*)feat_r, grad_disp_l, grad_disp_r, grad_left,
+                                                       grad_right, batch, channels, max_disp, height, width, temperature, out_height,
+                                                       out_width, disp_scale, s);
+    if (e != hipSuccess) return hip_fail(e, "soft disparity read-out backward launch");
+    return S3R_OK;
+}
+
+static int disp_loss_dims(int batch, int64_t pixels, float beta) {
+    if (!(beta >= 0.f) || !std::isfinite(beta))
+        return fail(S3R_ERR_INVALID, "disparity loss: beta must be finite and >= 0 (got %g)", (double)beta);
+    if (batch < 0 || pixels <= 0)
+        return fail(S3R_ERR_INVALID, "disparity loss dims: batch >= 0 and pixels > 0 (batch %d, pixels %lld)", batch, (long long)pixels);
+    if (pixels >= kMaxElems || (int64_t)batch * pixels >= kMaxElems || 4 * (int64_t)batch * pixels >= kMaxBytes)
+        return fail(S3R_ERR_INVALID, "tensor of 2^31 elements or more: split the batch");
+    return S3R_OK;
+}
+
+int s3r_disparity_loss_forward(const float* pred, const float* gt, float beta, float* loss_sum, int32_t* count, float* loss_elem,
+                               int batch, int64_t pixels, void* hip_stream) {
+    int rc = disp_loss_dims(batch, pixels, beta);
+    if (rc) return rc;
+    if (batch == 0) return S3R_OK;
+    if (!pred || !gt || !loss_sum || !count) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    hipStream_t s = (hipStream_t)hip_stream;
+    const double n = (double)batch * (double)pixels;
+    ProfScope ps(s, F_DISP, 5, 0.0, 4.0 * (n * (loss_elem ? 3.0 : 2.0) + 2.0 * batch));
+    hipError_t e = s3r::launch_disparity_loss(pred, gt, beta, loss_sum, count, loss_elem, batch, pixels, s);
+    if (e != hipSuccess) return hip_fail(e, "disparity loss launch");
+    return S3R_OK;
+}
+
+int s3r_disparity_loss_backward(const float* pred, const float* gt, const float* grad_scale, float beta, float* grad_pred, int batch,
+                                int64_t pixels, void* hip_stream) {
+    int rc = disp_loss_dims(batch, pixels, beta);
+    if (rc) return rc;
+    if (batch == 0) return S3R_OK;
+    if (!pred || !gt || !grad_scale || !grad_pred) return fail(S3R_ERR_INVALID, "null tensor pointer");
+    hipStream_t s = (hipStream_t)hip_stream;
+    ProfScope ps(s, F_DISP, 6, 0.0, 4.0 * (3.0 * batch * (double)pixels + batch));
+    hipError_t e = s3r::launch_disparity_loss_backward(pred, gt, grad_scale, beta, grad_pred, batch, pixels, s);
+    if (e != hipSuccess) return hip_fail(e, "disparity loss backward launch");
     return S3R_OK;
 }
 

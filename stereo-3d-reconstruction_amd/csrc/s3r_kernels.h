@@ -371,6 +371,17 @@ hipError_t launch_disparity_soft(const void* fl, const void* fr, int bf16, float
                                  int C, int D, int H, int W, float tau, int OH, int OW, float disp_scale, hipStream_t s);
 hipError_t launch_disparity_metrics(const float* pred, const float* gt, float* epe, int* counts, int B, int64_t S,
                                     hipStream_t s);
+// s3r_disparity_bwd.hip: the soft read-out's backward (fp32 NCHW features; gdl or gdr may be NULL: zeros; gl or gr may be NULL: not
+// computed), one workgroup per (sample, feature row); its LDS stays within disparity_soft_lds_bytes, the limit the API checks
+hipError_t launch_disparity_soft_backward(const float* fl, const float* fr, const float* gdl, const float* gdr, float* gl, float* gr,
+                                          int B, int C, int D, int H, int W, float tau, int OH, int OW, float disp_scale,
+                                          hipStream_t s);
+// s3r_disparity_loss.hip: masked smooth-L1 on disparity maps with a per-sample sum in launch_voxel_bce's order and the count of valid
+// pixels (loss_elem may be NULL), and its elementwise gradient
+hipError_t launch_disparity_loss(const float* pred, const float* gt, float beta, float* loss_sum, int* count, float* loss_elem, int B,
+                                 int64_t P, hipStream_t s);
+hipError_t launch_disparity_loss_backward(const float* pred, const float* gt, const float* gscale, float beta, float* gpred, int B,
+                                          int64_t P, hipStream_t s);
 
 #if defined(__HIPCC__)
 // Winograd F(4, 3) input transform along one axis (s3r_conv_wino.hip): the six class values of six consecutive padded rows.

@@ -902,6 +902,21 @@ class _DisparityMixin:
             parts.append(disparity_soft(feats[:b], feats[b:], self.cost_volume.max_disp, tau, size, scale, confidence))
         return tuple(p[0] if len(parts) == 1 else torch.cat(p, 0) for p in zip(*parts))
 
+    def differentiable_disparity(self, left: torch.Tensor, right: torch.Tensor, in_pixels: bool = True,
+                                 temperature: Optional[float] = None, full_resolution: bool = False, batch_stats: bool = False):
+        """`disparity(readout="soft")`'s (left, right) disparity maps recorded for autograd on the encoder's parameters: the encoder
+        through `encoder.differentiable_pair` (B <= MAX_CHUNK pairs, fp32 models only; batch_stats as there), then
+        `differentiable_disparity_soft` with the scaling rules of `disparity`: (B,28,28), or (B,224,224) upsampled bilinearly when
+        full_resolution; in_pixels scales to 224x224 render pixels (x8), the unit of the dataset's EXR ground truth; temperature
+        defaults to the `disparity_temperature` attribute.  A training step on the disparity ground truth:
+        `dl, dr = model.differentiable_disparity(l, r, full_resolution=True); (DisparityLoss()(dl, gt_l) + DisparityLoss()(dr, gt_r)).backward()`."""
+        tau = float(self.disparity_temperature if temperature is None else temperature)
+        feats = self.encoder.differentiable_pair(left, right, batch_stats)
+        b = feats.shape[0] // 2
+        scale = float(spec.IMG_HW // spec.FEAT_HW) if in_pixels else 1.0
+        size = (spec.IMG_HW, spec.IMG_HW) if full_resolution else None
+        return differentiable_disparity_soft(feats[:b], feats[b:], self.cost_volume.max_disp, tau, size, scale)
+
     @torch.no_grad()
     def stereo_features(self, left: torch.Tensor, right: torch.Tensor):
         """(feat_left, feat_right), (B,32,28,28) fp32 each: the FROZEN encoder without a graph — the two maps `forward` feeds the cost
@@ -2004,6 +2019,180 @@ def disparity_soft(feat_l: torch.Tensor, feat_r: torch.Tensor, max_disp: int = s
                                                   Cc, H, W, int(max_disp), float(temperature), OH, OW, float(scale),
                                                   _stream_ptr(dev)), "disparity_soft")
     return tuple(outs)
+
+
+def _check_soft_features(feat_l, feat_r, who):
+    if not isinstance(feat_l, torch.Tensor) or not isinstance(feat_r, torch.Tensor) or feat_l.dim() != 4 or feat_l.shape != feat_r.shape:
+        raise RuntimeError(f"{who}: feat_l / feat_r must be two (B,C,H,W) tensors of one shape")
+    if feat_l.dtype != torch.float32 or feat_r.dtype != torch.float32:
+        raise RuntimeError(f"{who} reads float32 (NCHW) features only (no bf16 backward exists), got {feat_l.dtype} / {feat_r.dtype}")
+    return (_check_input(feat_l.detach(), "feat_l", feat_l.shape[1:]), _check_input(feat_r.detach(), "feat_r", feat_r.shape[1:]))
+
+
+@torch.no_grad()
+def disparity_soft_backward(feat_l: torch.Tensor, feat_r: torch.Tensor, grad_disp_l: Optional[torch.Tensor],
+                            grad_disp_r: Optional[torch.Tensor], max_disp: int = spec.MAX_DISP, temperature: float = 1.0,
+                            out_size: Optional[Sequence[int]] = None, scale: float = 1.0, need_left: bool = True,
+                            need_right: bool = True):
+    """(grad_left, grad_right), (B,C,H,W) each and `None` for the side not asked for, of `disparity_soft`'s two disparity maps for their
+    gradients grad_disp_l / grad_disp_r (B,*out_size) (either may be None: zeros): ONE `s3r_disparity_soft_backward` call with the
+    forward's max_disp, temperature, out_size and scale.  Nothing is saved by the forward: the kernel recomputes the costs and the softmax.
+    Every output element is its own sequential fp32 sum in ascending d and the upsample's adjoint is a gather in a fixed order (no
+    atomics: the same bits on every run and for every batch a sample appears in).  fp32 features only."""
+    if not (need_left or need_right):
+        raise RuntimeError("disparity_soft_backward needs need_left or need_right")
+    if grad_disp_l is None and grad_disp_r is None:
+        raise RuntimeError("disparity_soft_backward needs grad_disp_l or grad_disp_r")
+    fl, fr = _check_soft_features(feat_l, feat_r, "disparity_soft_backward")
+    B, Cc, H, W = fl.shape
+    OH, OW = (H, W) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    grads = [None if g is None else _check_input(g.detach(), name, (OH, OW))
+             for g, name in ((grad_disp_l, "grad_disp_l"), (grad_disp_r, "grad_disp_r"))]
+    if any(g is not None and g.shape[0] != B for g in grads):
+        raise RuntimeError(f"disparity_soft_backward: the disparity gradients must be ({B},{OH},{OW})")
+    gl = torch.empty(fl.shape, dtype=torch.float32, device=fl.device) if need_left else None
+    gr = torch.empty(fl.shape, dtype=torch.float32, device=fl.device) if need_right else None
+    if B:
+        ptr = [None if t is None else t.data_ptr() for t in grads + [gl, gr]]
+        _lib.check(_lib.load().s3r_disparity_soft_backward(fl.data_ptr(), fr.data_ptr(), _lib.DTYPE["fp32"], *ptr, B, Cc, H, W,
+                                                           int(max_disp), float(temperature), OH, OW, float(scale),
+                                                           _stream_ptr(fl.device)), "disparity_soft backward")
+    return gl, gr
+
+
+class _DisparitySoftFunction(torch.autograd.Function):
+    """`disparity_soft`'s two disparity maps with `disparity_soft_backward` as their derivative; saves the two feature maps only"""
+
+    @staticmethod
+    def forward(ctx, feat_l, feat_r, max_disp, temperature, size, scale):
+        fl, fr = _check_soft_features(feat_l, feat_r, "differentiable_disparity_soft")
+        ctx.save_for_backward(feat_l, feat_r)
+        ctx.args = (int(max_disp), float(temperature), None if size is None else (int(size[0]), int(size[1])), float(scale))
+        dl, dr = disparity_soft(fl, fr, ctx.args[0], ctx.args[1], ctx.args[2], ctx.args[3])
+        return dl, dr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_l, grad_r):
+        need_l, need_r = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_l or need_r):
+            return None, None, None, None, None, None
+        feat_l, feat_r = ctx.saved_tensors
+        max_disp, tau, size, scale = ctx.args
+        gl, gr = disparity_soft_backward(feat_l, feat_r, grad_l.contiguous().float(), grad_r.contiguous().float(), max_disp, tau, size,
+                                         scale, need_l, need_r)
+        return gl, gr, None, None, None, None
+
+
+def differentiable_disparity_soft(feat_l: torch.Tensor, feat_r: torch.Tensor, max_disp: int = spec.MAX_DISP, temperature: float = 1.0,
+                                  size: Optional[Sequence[int]] = None, scale: float = 1.0):
+    """`disparity_soft`'s (disp_l, disp_r) recorded for autograd: the values have the bits of `disparity_soft` (the same kernel call), the
+    backward is `disparity_soft_backward`, called with exactly the sides autograd needs (`needs_input_grad` of the two maps).  fp32
+    features (B,C,H,W); size=None: (B,H,W) maps, else (B,*size) upsampled bilinearly; disparities are multiplied by `scale`.  The
+    confidence maps are not returned (they get no gradient), and the temperature is a constant."""
+    return _DisparitySoftFunction.apply(feat_l, feat_r, max_disp, temperature, size, scale)
+
+
+def _check_disparity_loss(pred, gt, beta, who):
+    if not isinstance(pred, torch.Tensor) or not isinstance(gt, torch.Tensor):
+        raise TypeError(f"{who}: pred and gt must be torch.Tensors")
+    if pred.dim() < 2 or pred.shape != gt.shape:
+        raise RuntimeError(f"{who} expects pred and gt of one shape (B, ...), got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    beta = float(beta)
+    if not (beta >= 0.0) or beta == float("inf"):
+        raise ValueError(f"{who}: beta must be finite and >= 0, got {beta}")
+    p = _check_input(pred.detach(), "pred", pred.shape[1:])
+    t = _check_input(gt.detach(), "gt", gt.shape[1:])
+    pixels = 1
+    for n in pred.shape[1:]:
+        pixels *= n
+    if pixels == 0:
+        raise RuntimeError(f"{who} needs non-empty samples")
+    return p, t, pred.shape[0], pixels, beta
+
+
+@torch.no_grad()
+def disparity_loss(pred: torch.Tensor, gt: torch.Tensor, beta: float = 1.0, elements: bool = False):
+    """(loss_sum (B), count (B) int32, loss_elem or None) of the smooth-L1 loss on the pixels whose ground truth is valid (finite and
+    >= 0, as `disparity_metrics`) (`s3r_disparity_loss_forward`): with e = pred - gt, l = 0.5 e^2 / beta where |e| < beta, else
+    |e| - 0.5 beta (beta = 0: plain L1); an invalid pixel counts as +0.0 and its values never enter arithmetic.  loss_sum[b] is the fp32
+    sum in `voxel_bce`'s fixed order (a function of the sample size only: the same bits in every batch split), count[b] the valid
+    pixels; loss_elem (the shape of pred) is returned with `elements=True`.  Records no graph (`differentiable_disparity_loss` does)."""
+    p, t, B, P, beta = _check_disparity_loss(pred, gt, beta, "disparity_loss")
+    s = torch.empty((B,), dtype=torch.float32, device=p.device)
+    n = torch.empty((B,), dtype=torch.int32, device=p.device)
+    e = torch.empty(p.shape, dtype=torch.float32, device=p.device) if elements else None
+    if B:
+        _lib.check(_lib.load().s3r_disparity_loss_forward(p.data_ptr(), t.data_ptr(), beta, s.data_ptr(), n.data_ptr(),
+                                                          None if e is None else e.data_ptr(), B, P, _stream_ptr(p.device)),
+                   "disparity_loss")
+    return s, n, e
+
+
+@torch.no_grad()
+def disparity_loss_backward(pred: torch.Tensor, gt: torch.Tensor, grad_scale: torch.Tensor, beta: float = 1.0) -> torch.Tensor:
+    """grad_pred (the shape of pred) of sum_b grad_scale[b] * loss_sum[b] (`s3r_disparity_loss_backward`): grad_scale[b] *
+    clamp((pred - gt) / beta, -1, 1) at a valid pixel (grad_scale[b] * sgn(pred - gt) at beta = 0), exactly +0.0 at an invalid one —
+    elementwise and bit for bit."""
+    p, t, B, P, beta = _check_disparity_loss(pred, gt, beta, "disparity_loss_backward")
+    gs = _check_input(grad_scale, "grad_scale", ())
+    if gs.shape[0] != B:
+        raise RuntimeError(f"grad_scale must have shape ({B},), got {tuple(gs.shape)}")
+    g = torch.empty(p.shape, dtype=torch.float32, device=p.device)
+    if B:
+        _lib.check(_lib.load().s3r_disparity_loss_backward(p.data_ptr(), t.data_ptr(), gs.data_ptr(), beta, g.data_ptr(), B, P,
+                                                           _stream_ptr(p.device)), "disparity_loss backward")
+    return g
+
+
+class _DisparityLossFunction(torch.autograd.Function):
+    """`disparity_loss`'s loss_sum with `disparity_loss_backward` as its derivative; the gradient goes to pred only.  count is returned
+    beside it as a constant."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, beta):
+        s, n, _ = disparity_loss(pred, gt, beta)
+        ctx.save_for_backward(pred, gt)
+        ctx.beta = float(beta)
+        ctx.mark_non_differentiable(n)
+        return s, n
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_sum, _grad_count):
+        pred, gt = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return disparity_loss_backward(pred, gt, grad_sum.contiguous().float(), ctx.beta), None, None
+
+
+def differentiable_disparity_loss(pred: torch.Tensor, gt: torch.Tensor, beta: float = 1.0):
+    """`disparity_loss`'s (loss_sum (B), count (B)) with loss_sum recorded for autograd: the same bits, with the elementwise backward
+    `disparity_loss_backward`.  The gradient goes to pred only (a ground truth is a constant of the loss)."""
+    return _DisparityLossFunction.apply(pred, gt, beta)
+
+
+class DisparityLoss(nn.Module):
+    """Smooth-L1 loss (torch.nn.SmoothL1Loss's rule with `beta`; beta = 0 is L1) of a disparity map against a ground truth with invalid
+    pixels: forward(pred, gt) with pred, gt (B,H,W) or any (B, ...) returns the mean over the VALID pixels of the batch (ground truth
+    finite and >= 0: the EXR maps mark background as inf or negative), `loss_sum.double().sum() / max(count.sum(), 1)` cast to fp32 —
+    the per-sample sums and counts are the HIP kernel's, the sums in its fixed order.  A batch without a valid pixel gives 0 and a
+    zero gradient.  With grad mode on and pred requiring grad the value (the same bits) is recorded for autograd through
+    `differentiable_disparity_loss`; otherwise nothing is recorded (as `VoxelBCELoss`)."""
+
+    def __init__(self, beta: float = 1.0):
+        super().__init__()
+        beta = float(beta)
+        if not (beta >= 0.0) or beta == float("inf"):
+            raise ValueError(f"DisparityLoss: beta must be finite and >= 0, got {beta}")
+        self.beta = beta
+
+    def forward(self, pred, gt):
+        if torch.is_grad_enabled() and isinstance(pred, torch.Tensor) and pred.requires_grad:
+            s, n = differentiable_disparity_loss(pred, gt, self.beta)
+        else:
+            s, n, _ = disparity_loss(pred, gt, self.beta)
+        return (s.double().sum() / n.sum().clamp(min=1).double()).float()
 
 
 @torch.no_grad()
