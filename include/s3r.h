@@ -804,7 +804,12 @@ typedef struct s3r_prof_record {
                            for the Winograd forms) */
     int32_t algo;       /* what ran: 0 direct, 1 Winograd serial form, 2 class-parallel form, 3 dual form, 4 two-axis form, 5 three-axis
                            form (transposed layers), 6 its class-parallel launch form */
-    int32_t reserved;
+    int32_t launch_form; /* how launch_conv_mfma sent a direct fp32 layer out (it picks these forms itself; no tile code or descriptor field
+                           forces them).  bit 0: a tail cut was planned (the layer's own tile over [0, n_cut), the rest re-tiled 64 x 64);
+                           bit 1: bulk and remainder went out as ONE launch (so a cut layer may report launches == 1); bit 2: a launch of
+                           this layer ran the 64 x 64 tile's six-stage ring (at most 384 workgroups).  A record that brackets several
+                           direct launches (sub-batches, residue classes) carries the OR of theirs.  0 for one plain launch and for
+                           every other family and algorithm: the field was `reserved`, always 0, before. */
 } s3r_prof_record;
 int s3r_profile_enable(int max_records);   /* 0 disables and frees the event pool */
 int s3r_profile_reset(void);

@@ -22,6 +22,7 @@ ABI_VERSION = 8
 CONV_BACKWARD_TAG = 1000000      # S3R_CONV_BACKWARD_TAG: a conv backward's profiler record carries this + the layer's tag
 ALGO_AUTO, ALGO_DIRECT, ALGO_WINOGRAD = 0, 1, 2
 ALGO = {None: 0, "auto": 0, "direct": 1, "winograd": 2, False: 1, True: 2}
+FORM_CUT, FORM_ONE_LAUNCH, FORM_RING = 1, 2, 4      # s3r_prof_record.launch_form (include/s3r.h)
 RAN = {0: "direct", 1: "winograd-serial", 2: "winograd-class-parallel", 3: "winograd-dual", 4: "winograd-2axis", 5: "winograd-3axis", 6: "winograd-3axis-class-parallel"}
 
 
@@ -39,7 +40,7 @@ class Layer(C.Structure):
 class ProfRecord(C.Structure):
     _fields_ = [("family", C.c_int32), ("tag", C.c_int32), ("ms", C.c_float), ("launches", C.c_int32),
                 ("flops", C.c_double), ("bytes", C.c_double), ("exec_flops", C.c_double), ("algo", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("launch_form", C.c_int32)]
 
 
 class S3RError(RuntimeError):
@@ -191,4 +192,4 @@ def profile_read(max_records=4096):
     buf = (ProfRecord * max_records)()
     n = check(load().s3r_profile_read(buf, max_records), "profile_read")
     return [dict(family=FAMILY.get(r.family, str(r.family)), tag=r.tag, ms=r.ms, launches=r.launches, flops=r.flops,
-                 bytes=r.bytes, exec_flops=r.exec_flops, ran=RAN.get(r.algo, str(r.algo))) for r in buf[:n]]
+                 bytes=r.bytes, exec_flops=r.exec_flops, ran=RAN.get(r.algo, str(r.algo)), launch_form=r.launch_form) for r in buf[:n]]

@@ -205,6 +205,7 @@ int conv_head_fused(const s3r_conv_desc* d, const Geo& g, const s3r_conv_desc* h
                  4.0 * d->batch * (double)hg.out_sp);
     hipError_t e = s3r::launch_conv_mfma(p, Ln.cfg + 16 * Ln.vec, s);
     ps.launches = s3r::conv_last_launch_count();
+    ps.form = s3r::conv_last_launch_form();
     if (e != hipSuccess) return hip_fail(e, "fused conv+head launch");
     return S3R_OK;
 }
@@ -437,6 +438,7 @@ int conv_forward_impl(const s3r_conv_desc* d, const void* xv, const void* x2v, i
                             e = s3r::launch_conv_mfma(c, Li.cfg + 16 * Li.vec, s);
                             if (e != hipSuccess) return hip_fail(e, "conv forward launch (unfolded)");
                             ps.launches += 1 + s3r::conv_last_launch_count();
+                            ps.form |= s3r::conv_last_launch_form();
                         }
                         ps.exec = 2.0 * d->batch * (double)d->cout * (double)g.out_sp * sg.cin_pad;
                         if (needs_act_pass(d)) {
@@ -468,6 +470,7 @@ int conv_forward_impl(const s3r_conv_desc* d, const void* xv, const void* x2v, i
                     e = s3r::launch_conv_mfma(c, L.cfg + 16 * L.vec, s);
                     if (e != hipSuccess) return hip_fail(e, "conv forward launch (depth-to-space)");
                     ps.launches += s3r::conv_last_launch_count();
+                    ps.form |= s3r::conv_last_launch_form();
                     ps.exec = 2.0 * (double)c.Ntotal * c.Cin * (double)c.Cout;
                 } else if (tclass_layer(d)) {
                     // ---- ConvTranspose, dilation 1: the residue classes of the output, each a stride-1 convolution — ONE launch over a
@@ -497,6 +500,7 @@ int conv_forward_impl(const s3r_conv_desc* d, const void* xv, const void* x2v, i
                         e = s3r::launch_conv_mfma(c, L.cfg + 16 * L.vec, s);
                         if (e != hipSuccess) return hip_fail(e, "conv forward launch (transposed class)");
                         ps.launches += s3r::conv_last_launch_count();
+                        ps.form |= s3r::conv_last_launch_form();
                     }
                     if (tab.n > 0) {
                         e = s3r::launch_conv_tcls(base, tab, s);
@@ -509,6 +513,7 @@ int conv_forward_impl(const s3r_conv_desc* d, const void* xv, const void* x2v, i
                     e = s3r::launch_conv_mfma(q, L.cfg + 16 * L.vec, s);
                     if (e != hipSuccess) return hip_fail(e, "conv forward launch");
                     ps.launches += s3r::conv_last_launch_count();
+                    ps.form |= s3r::conv_last_launch_form();
                 }
                 if (needs_act_pass(d)) {
                     s3r::AuxScope aux(s, 8.0 * (double)g.y_elems);
@@ -610,6 +615,7 @@ int conv_forward_impl(const s3r_conv_desc* d, const void* xv, const void* x2v, i
             ProfScope ps(s, F_MFMA, d->tag, g.flops, g.bytes);
             e = s3r::launch_conv_mfma(p, L.cfg + 16 * L.vec, s);
             ps.launches = s3r::conv_last_launch_count();
+            ps.form = s3r::conv_last_launch_form();
             if (e == hipSuccess && needs_act_pass(d)) {       // (make_params ran the kernel with ACT_NONE; split-K as the descriptor says)
                 s3r::AuxScope aux(s, 8.0 * (double)g.y_elems);
                 e = s3r::launch_act(y, g.y_elems, d->act, d->act_param, s);

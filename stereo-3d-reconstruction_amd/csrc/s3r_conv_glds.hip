@@ -651,6 +651,8 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(const ConvParams p, in
 
 static thread_local int g_launch_count = 0;          // kernels launched by the last launch_conv_mfma (split-K finish included)
 int conv_last_launch_count() { return g_launch_count; }
+static thread_local int g_launch_form = 0;           // s3r_prof_record.launch_form of the last launch_conv_mfma: 1 cut, 2 one launch, 4 ring
+int conv_last_launch_form() { return g_launch_form; }
 
 hipError_t launch_conv_finish(const ConvParams& p, int npad, hipStream_t stream) {
     g_launch_count += 1;
@@ -860,6 +862,7 @@ static hipError_t launch_vec(const ConvParams& p, int vec, hipStream_t stream) {
     }
     if constexpr (WM == 2 && WN == 2 && TM == 1 && TN == 1) {
         if (sparse_launch(p, 64, 64)) {
+            g_launch_form |= 4;
             switch (vec) {
                 case 4: return launch_cfg<WM, WN, TM, TN, 4, false, 6>(p, stream);
                 case 1: return launch_cfg<WM, WN, TM, TN, 1, false, 6>(p, stream);
@@ -927,6 +930,7 @@ static bool plan_tail_cut(const ConvParams& p, int cfg, int* n_cut) {
 hipError_t launch_conv_mfma(const ConvParams& pin, int code, hipStream_t stream) {
     ConvParams p = pin;
     g_launch_count = 0;
+    g_launch_form = 0;
     int cfg = code & 15;
     int vec = code >> 4;
     if (cfg == 15) cfg = conv_pick_tile(p);
@@ -952,11 +956,14 @@ hipError_t launch_conv_mfma(const ConvParams& pin, int code, hipStream_t stream)
     static const bool no_cut = getenv("S3R_NO_TAIL_CUT") != nullptr;      // tuning / A-B switch
     if (!p.head_w && !no_cut && plan_tail_cut(p, cfg, &n_cut)) {
         static const bool no_dual = getenv("S3R_NO_DUAL") != nullptr;         // A/B switch: bulk and remainder as two launches
+        g_launch_form |= 1;
         if (!no_dual && !p.transposed && p.Cout > 32) {
             g_launch_count += 1;
+            g_launch_form |= 2;
             const hipError_t ed = launch_dual(p, cfg, n_cut, vec, stream);
             if (ed != hipErrorNotSupported) return ed;
             g_launch_count -= 1;
+            g_launch_form &= ~2;
         }
         p.n_end = n_cut;
         hipError_t e = launch_tile(p, cfg, vec, stream);

@@ -34,6 +34,7 @@ struct ProfScope {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int launches = 1;     // kernel launches inside the scope (a conv may be cut into bulk + remainder, + split-K finish)
     int algo = 0;         // what ran: 0 direct, 1 / 2 / 3 the Winograd serial / class-parallel / dual form, 4 the two-axis algorithm
+    int form = 0;         // s3r_prof_record.launch_form: OR of conv_last_launch_form() over the scope's direct launches
     double exec = -1.0;   // MFMA FLOPs executed (< 0: the algorithmic count)
     int family, prev_tag = 0;
     hipStream_t stream;

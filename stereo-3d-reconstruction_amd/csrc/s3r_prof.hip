@@ -33,7 +33,7 @@ ProfScope::ProfScope(hipStream_t s, int fam, int tag, double flops, double bytes
     slot = (int)g_prof.rec.size();
     s3r_prof_record r;
     r.family = fam; r.tag = tag; r.ms = 0.f; r.flops = flops; r.bytes = bytes; r.launches = 1;
-    r.exec_flops = flops; r.algo = 0; r.reserved = 0;
+    r.exec_flops = flops; r.algo = 0; r.launch_form = 0;
     g_prof.rec.push_back(r);
     gen = g_prof.gen;
     e0 = g_prof.ev[2 * slot];
@@ -51,6 +51,7 @@ ProfScope::~ProfScope() {
     if (slot < (int)g_prof.rec.size()) {
         g_prof.rec[slot].launches = launches;
         g_prof.rec[slot].algo = algo;
+        g_prof.rec[slot].launch_form = form;
         if (exec >= 0.0) g_prof.rec[slot].exec_flops = exec;
     }
 }

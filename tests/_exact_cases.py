@@ -180,11 +180,12 @@ BF16_KINDS = {
     "cout100_s2": (L("t", "conv3d", 32, 100, 3, 2, 1), 9, 2, 0),
     "c128_cout128_ks2": (L("t", "conv3d", 128, 128, 3, 1, 1), 6, 2, 2),
 }
-BF16_TILES = (1, 2, 3, 4, 5, 6, 9, 10, 17, 18, 19, 21, 22, 23)
+BF16_TILES = (1, 2, 3, 4, 5, 6, 9, 10, 17, 18, 19, 20, 21, 22, 23)
 
 
 def bf16_refused(tm, kind):
-    """tests/test_bf16_gpu.py::test_bf16_tiles_and_split_k's refusal rules, verbatim"""
+    """tests/test_bf16_gpu.py::test_bf16_tiles_and_split_k's refusal rules, verbatim.  (20 — 512-position per-tap tiles with 32-channel
+    K tiles — has none, like 1, 2, 4, 17 and 18: one 64-cout tile per workgroup, no reuse image to fit)"""
     layer, n_in, B, ks = BF16_KINDS[kind]
     kc = 64 if tm in (5, 6) else 32
     plane_ok = (layer.s == 1 or layer.op == "deconv3d") and layer.cin % kc == 0 and (ks == 0 or (layer.cin // kc) % ks == 0)

@@ -38,7 +38,7 @@ _Static_assert(offsetof(s3r_prof_record, family) == 0 && offsetof(s3r_prof_recor
                offsetof(s3r_prof_record, ms) == 8 && offsetof(s3r_prof_record, launches) == 12 &&
                offsetof(s3r_prof_record, flops) == 16 && offsetof(s3r_prof_record, bytes) == 24 &&
                offsetof(s3r_prof_record, exec_flops) == 32 && offsetof(s3r_prof_record, algo) == 40 &&
-               offsetof(s3r_prof_record, reserved) == 44, "s3r_prof_record field offsets");
+               offsetof(s3r_prof_record, launch_form) == 44, "s3r_prof_record field offsets");
 _Static_assert(S3R_OK == 0 && S3R_ERR_INVALID == -1 && S3R_ERR_HIP == -2 && S3R_ERR_WORKSPACE == -3, "status codes");
 _Static_assert(S3R_OP_CONV == 0 && S3R_OP_DECONV == 1 && S3R_OP_LINEAR == 2, "op codes");
 _Static_assert(S3R_LAYOUT_PLAIN == 0 && S3R_LAYOUT_WINO_H == 2 && S3R_LAYOUT_WINO_DH == 3 && S3R_LAYOUT_WINO_HW == 4, "layouts");

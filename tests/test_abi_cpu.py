@@ -32,7 +32,7 @@ def test_header_symbols_all_exported(s3r, lib):
 def test_struct_layouts_match_header(s3r):
     assert C.sizeof(s3r._lib.ConvDesc) == 22 * 4     # ABI 7: + algo; ABI 8: + dilation, out_pad, act_param
     assert C.sizeof(s3r._lib.Layer) == 22 * 4 + 3 * 8
-    assert C.sizeof(s3r._lib.ProfRecord) == 48      # 4 x 4 bytes + 3 doubles + algo + reserved
+    assert C.sizeof(s3r._lib.ProfRecord) == 48      # 4 x 4 bytes + 3 doubles + algo + launch_form
     header = open(os.path.join(ROOT, "include", "s3r.h")).read()
     body = header[header.index("typedef struct s3r_conv_desc {"):header.index("} s3r_conv_desc;")]
     fields = re.findall(r"(?:int32_t|float)\s+([a-z_, ]+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S))

@@ -75,10 +75,10 @@ def test_each_layer_bf16_vs_oracle(s3r, oracle, idx, mfma_shape):
     assert (err <= 2.0 ** -7 * want.abs() + 1e-3 * want.abs().max()).all(), layer.name
 
 
-# 1, 2, 4: per-tap gather (64-channel K tiles where Cin allows, +16 = 32-channel), 3: its 128 x 128-cout tile;
+# 1, 2, 4: per-tap gather (64-channel K tiles where Cin allows, +16 = 32-channel: 17, 18, 20 — never refused), 3 / 19: its 128 x 128-cout tile;
 # 5, 6 / 21, 22: plane-reuse gather, 23: its 256 x 128-cout tile;
 # 9, 10: row-reuse gather (x128 / x256 positions)
-@pytest.mark.parametrize("tm", [1, 2, 3, 4, 5, 6, 9, 10, 17, 18, 19, 21, 22, 23])
+@pytest.mark.parametrize("tm", [1, 2, 3, 4, 5, 6, 9, 10, 17, 18, 19, 20, 21, 22, 23])
 @pytest.mark.parametrize("kind", ["conv3d_s1", "conv3d_s2", "deconv", "conv2d_s2", "conv3d_k4_valid_ks2", "cout32",
                                   "conv2d_s1_w28", "conv3d_s1_w14", "conv3d_s1_c64", "deconv_c64", "deconv_c128_w8",
                                   "conv3d_k4_valid_c128_ks2", "conv2d_s1_c128_w9", "cout36_narrow_stores", "cout100_s2", "c128_cout128_ks2"])

@@ -21,8 +21,8 @@ A mismatch is reported as the first differing element with its (b, cout, positio
 difference in lattice units (2^-f): a difference equal to one `w x` product names the tap.
 
 Cases: direct fp32 233 (18 network layers x B 1 / 3, 8 shapes x 8 tiles x 2 gather widths, split-K 1 / 2 / 4 and v5 / v6 / d1 at
-network size under split-K 1 .. 16, the general-layer families), linear 28, bf16 260 under each of the two matrix instructions
-(18 layers x B 1 / 3, the 14 x 16 tile matrix), Winograd 48 (one-axis x 3 launch forms, two-axis tiles 3 / 4 / 5 incl. F(2,4) x F(2,4),
+network size under split-K 1 .. 16, the general-layer families), linear 28, bf16 276 under each of the two matrix instructions
+(18 layers x B 1 / 3, the 15 x 16 tile matrix), Winograd 48 (one-axis x 3 launch forms, two-axis tiles 3 / 4 / 5 incl. F(2,4) x F(2,4),
 transposed F(2,2) classes and the three-axis form), Winograd at ragged shapes and at the LDS limits 143 (tests/_exact_cases.py::
 _wino_shapes: the smallest shapes at which each branch of those kernels is taken — edges with n mod 4 = 1, 2, 3 and the dword-gather
 instantiation of the one-axis kernel, F(2,4) x F(2,4) at output edges 2, 3, 5, 6, couts 2 / 33 / 70 / 130, ragged last packs of the
