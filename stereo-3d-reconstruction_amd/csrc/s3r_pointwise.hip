@@ -658,7 +658,11 @@ __global__ __launch_bounds__(256) void linear_finish4_kernel(const float* __rest
 }
 
 // one thread per output; the ksplit partial slabs are summed in kz order (a fixed order: deterministic) with eight loads
-// in flight per thread (a one-load-at-a-time loop is a chain of ksplit L2 round trips: 64 of them for p1)
+// in flight per thread (a one-load-at-a-time loop is a chain of ksplit L2 round trips: 64 of them for p1).
+// NOT REACHED TODAY: launch_linear sends every ksplit >= 16 to linear_finish4_kernel and linear_split only makes powers of two, so
+// this kernel sees ksplit 1, 2, 4 or 8 and the eight-at-a-time loop (z + 8 <= ksplit from z = 1: ksplit >= 9) never runs — only
+// the scalar tail does.  No test executes that loop (tests/test_linear_plan_cpu.py pins ksplit <= 8 here); it stays for a split
+// rule that makes a ksplit in 9 .. 15.
 __global__ __launch_bounds__(256) void linear_finish_kernel(const float* __restrict__ part, float* __restrict__ y,
                                                             const float* __restrict__ scale, const float* __restrict__ bias,
                                                             int Cout, long long total, int ksplit, int act) {

@@ -277,27 +277,39 @@ def cost_volume_planes(s3r, lib, shape, kind):
 
 
 # ---------------------------------------------------------------- linear
-def linear_forward(s3r, lib, shape, act):
+def linear_forward(s3r, lib, shape, act, bias=True):
+    """bias=False: the call is made with bias = NULL (include/s3r.h: NULL = 0) and held to the reference without a shift"""
     B, cin, cout = shape
     l = s3r.arch_spec.Layer("t", "linear", cin, cout, 1, 1, 0, False, act)
     p = R.make_params(l, cin + cout, DEV)
+    if not bias:
+        p["shift"] = None
     x = torch.randn(B, cin, generator=torch.Generator().manual_seed(B)).to(DEV)
     xb = G.Guarded("x", x.shape, torch.float32, DEV, "in", data=x)
     wb = G.Guarded("w", p["w"].shape, torch.float32, DEV, "in", data=p["w"])
-    bb = G.Guarded("bias", cout, torch.float32, DEV, "in", data=p["shift"])
+    bb = G.Guarded("bias", cout, torch.float32, DEV, "in", data=p["shift"]) if bias else None
     need = lib.s3r_linear_scratch_elems(B, cin, cout)
     outs = []
     for fill in ("nan", "zero"):
         y = G.Guarded("y", (B, cout), torch.float32, DEV, "out")
         scr = G.Guarded("scratch", need, torch.float32, DEV, "scratch", fill=fill)
-        _rc(lib, lib.s3r_linear_forward(xb.ptr, wb.ptr, bb.ptr, y.ptr, B, cin, cout, s3r._lib.ACT[act], scr.ptr, need, None), "linear")
+        _rc(lib, lib.s3r_linear_forward(xb.ptr, wb.ptr, bb.ptr if bias else None, y.ptr, B, cin, cout, s3r._lib.ACT[act], scr.ptr, need,
+                                        None), "linear")
         _sync()
-        G.check_all(xb, wb, bb, y, scr)
+        G.check_all(xb, wb, y, scr, *([bb] if bias else []))
         outs.append(y.t.clone())
     assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32))
     ref, mag = R.ref64(l, x, p)
     check_values(l, "direct", outs[0], ref, mag, shape)
     return outs[0]
+
+
+def linear_descriptor(s3r, lib, shape, act):
+    """the same layer as an S3R_OP_LINEAR descriptor through s3r_conv_pack_weights + s3r_conv_forward, with a folded BatchNorm: the
+    one route on which the linear kernels' scale[o] branch holds a vector"""
+    B, cin, cout = shape
+    l = s3r.arch_spec.Layer("t", "linear", cin, cout, 1, 1, 0, True, act)
+    return conv_forward_ref64(s3r, lib, BC.ConvCase("linear-desc-" + "x".join(map(str, shape)) + "-" + act, l, 1, B))
 
 
 # ---------------------------------------------------------------- Chamfer, IoU, disparity, channels-last hand-off

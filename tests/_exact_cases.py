@@ -16,6 +16,7 @@ from s3r import arch_spec as spec
 
 from tests import _buffer_cases as BC
 from tests import _lattice as LT
+from tests import _linear_cases as LC
 from tests import _ref64 as R
 
 L = spec.Layer
@@ -34,9 +35,11 @@ class Data:
     density: float = 1.0
     dtype: str = "fp32"
     xdensity: float = 1.0
+    ep: str = "ss"             # the epilogue's vector form (tests/_lattice.py::lattice_case): "0s" scale NULL, "s0" shift NULL, "00" both
 
     def make(self):
-        return LT.lattice_case(self.layer, self.B, self.n_in, self.seed, self.form, self.xmax, self.wmax, self.density, self.xdensity)
+        return LT.lattice_case(self.layer, self.B, self.n_in, self.seed, self.form, self.xmax, self.wmax, self.density, self.xdensity,
+                               self.ep)
 
     @property
     def bf16_out(self):
@@ -46,7 +49,7 @@ class Data:
     def id(self):
         l = self.layer
         return (f"{l.name}-{l.op}-{l.cin}to{l.cout}-k{l.k}s{l.s}p{l.p}d{l.dil}o{l.opad}-{l.act}{l.act_param or ''}-e{self.n_in}-B{self.B}-"
-                f"{self.dtype}-{self.form}-x{self.xmax}w{self.wmax}-s{self.seed}")
+                f"{self.dtype}-{self.form}-x{self.xmax}w{self.wmax}-s{self.seed}" + ("" if self.ep == "ss" else f"-ep{self.ep}"))
 
 
 @dataclass(frozen=True)
@@ -156,6 +159,10 @@ def _linear():
     for i, l in enumerate(spec.POINT_HEAD):
         for B in (1, 3):
             out.append(XCase(f"{l.name}-B{B}", Data(l, B, 1, 510 + i), twice=True))
+    # every branch of the launch plan (tests/_linear_cases.py::SWEEP holds the reason for each shape)
+    for B, cin, cout in LC.SWEEP:
+        for act in ("none", "relu"):
+            out.append(XCase(f"linear-{B}x{cin}x{cout}-{act}", Data(L("t", "linear", cin, cout, 1, 1, 0, False, act), B, 1, 522), twice=True))
     return out
 
 
@@ -351,6 +358,68 @@ def _wino_shapes():
 WINO_SHAPE_CASES = _wino_shapes()
 
 
+# ---------------------------------------------------------------- every epilogue site under the four vector forms
+THREE_AXIS_RAN = ("winograd-3axis", "winograd-3axis-class-parallel")
+
+
+def three_axis_ran(tile):
+    """s3r_plan.hip, resolve_algo: tile 6 the library's launch form (either), 7 class-parallel, 8 the one-kernel form: both run"""
+    return {6: THREE_AXIS_RAN, 7: THREE_AXIS_RAN[1:], 8: THREE_AXIS_RAN[:1]}[tile]
+
+
+def _ep_sites():
+    """(site, dtype route, the site's Data in the "ss" form, [(launch, XCase keywords)]): the smallest shape the suite has for each
+    kernel that ends in `scale ? scale[m] : 1, shift ? shift[m] : 0`, forced onto that kernel by algo / tile / ksplit.  Layers that
+    fold no BatchNorm elsewhere in the suite (head, linear) get bn=True here, so that their scale[] branch holds a real vector"""
+    c2 = lambda ci, co: L("t", "conv2d", ci, co, 3, 1, 1)
+    c3 = lambda ci, co: L("t", "conv3d", ci, co, 3, 1, 1)
+    up = lambda ci, co: L("t", "deconv3d", ci, co, 4, 2, 1)
+    seed = 940
+    two = ("winograd-2axis",)
+    sites = [
+        ("direct", Data(L("t", "conv3d", 64, 33, 3, 2, 1), 2, 9, seed),
+         [("epilogue", dict(ksplit=1, algo=DIRECT)), ("splitk2-finish", dict(ksplit=2, algo=DIRECT))]),
+        ("tclass", Data(L("t", "deconv2d", 32, 7, 4, 2, 1), 2, 7, seed), [("residue-classes", {})]),
+        ("d2s", Data(L("t", "deconv2d", 32, 24, 3, 3, 0), 2, 7, seed), [("depth-to-space", {})]),
+        ("wino1", _wino_data(c2(32, 33), 3, 5, seed, "f43-h"),
+         [(f"tile{t}", dict(tile=t, algo=WINO, ran=(ONE_AXIS_RAN[t],) if t < 2 else ONE_AXIS_RAN)) for t in (0, 1, 2)]),
+        ("wino2-conv2d", _wino_data(c2(32, 33), 3, 4, seed, "f43x2"), [(f"tile{t}", dict(tile=t, algo=WINO, ran=two)) for t in (3, 4, 5)]),
+        ("wino2-conv3d", _wino_data(c3(32, 40), 3, 4, seed, "f43x2"), [(f"tile{t}", dict(tile=t, algo=WINO, ran=two)) for t in (3, 4, 5)]),
+        ("wino2-k4", _wino_data(L("t", "conv3d", 32, 48, 4, 1, 0), 3, 5, seed, "f24x2"),
+         [(f"tile{t}", dict(tile=t, algo=WINO, ran=two)) for t in (3, 4)]),
+        ("dwino2", Data(up(32, 24), 3, 4, seed, "f22x2"),
+         [(f"tile{t}", dict(tile=t, algo=WINO, ran=(ONE_AXIS_RAN[t],) if t < 2 else ONE_AXIS_RAN)) for t in (0, 1, 2)]),
+        ("dwino3", Data(up(16, 40), 3, 8, seed, "f22x3"), [(f"tile{t}", dict(tile=t, algo=WINO, ran=three_axis_ran(t))) for t in (6, 7, 8)]),
+        ("head", Data(L("t", "conv2d", 48, 1, 1, 1, 0, True, "relu"), 3, 6, seed + 1, wmax=2), [("kernel", {})]),      # (one channel: a seed with scale != 1)
+    ]
+    for name, (B, cin, cout) in LC.PER_KERNEL.items():          # an S3R_OP_LINEAR descriptor: the route that has a scale
+        sites.append((f"linear-{name}", Data(L("t", "linear", cin, cout, 1, 1, 0, True, "relu"), B, 1, seed), [("descriptor", {})]))
+    sites += [
+        ("bf16-mfma", _bf16_data(c3(32, 96), 3, 7, seed), [("epilogue", {})]),
+        ("bf16-splitk", _bf16_data(L("t", "conv3d", 64, 40, 4, 1, 0), 2, 7, seed), [("splitk2-finish", dict(ksplit=2))]),
+        ("bf16-head", _bf16_data(L("t", "conv3d", 64, 1, 1, 1, 0, True, "relu"), 3, 4, seed), [("kernel", {})]),
+    ]
+    return sites
+
+
+def _ep_cases():
+    cases, groups = [], []
+    for site, d, launches in _ep_sites():
+        forms = [dataclasses.replace(d, ep=ep) for ep in LT.EP_FORMS]
+        groups.append((site, forms))
+        for f in forms:
+            for tag, kw in launches:
+                cases.append(XCase(f"ep-{site}-{tag}-{f.ep}", f, twice=True, **kw))
+    return cases, groups
+
+
+EP_CASES, EP_GROUPS = _ep_cases()
+# s3r_linear_forward has no scale: bias = NULL is its one other form, once per kernel of the plan (the given-bias run is the sweep's)
+LINEAR_NULL_BIAS = [XCase(f"linear-{name}-{B}x{cin}x{cout}-null-bias",
+                          Data(L("t", "linear", cin, cout, 1, 1, 0, False, "relu"), B, 1, 522, wmax=4 if cin < 64 else 1, ep="00"), twice=True)
+                    for name, (B, cin, cout) in LC.PER_KERNEL.items()]
+
+
 def auto_form(c):
     """the Winograd form include/s3r.h's policy resolves an AUTO convolution of the sweep to: the two-axis algorithm for every stride-1
     layer that has it and an edge <= 28, the one-axis kernel above"""
@@ -396,16 +465,30 @@ CV_CASES = _cv()
 
 @dataclass(frozen=True)
 class ChainCase:
-    """two layers through s3r_chain_forward; the first has scale 1 / shift 0 / ReLU, so the intermediate stays on the integer lattice"""
+    """two layers through s3r_chain_forward; the first has a ReLU and an epilogue that keeps the intermediate on the integer lattice.
+    pep, the producer's epilogue: "unit" scale 1 / shift 0 as vectors; "null" both NULL; "int" scale in {1, 2} and an integer shift
+    in [-4, 8] per channel (seeded by the first Data's seed)"""
     id: str
     first: Data
     second: Data               # (its x is the first layer's output: only the parameters of second.make() are used)
     dtype: str = "fp32"
+    pep: str = "unit"
+    algo: int = 0              # of the first layer
+    tile: int = -1
+    ran: tuple = ()            # the first layer's profiler record must name one of these; (): not asserted
+    fused: bool = False        # the head must have run inside the first layer's launch: no head record
 
     def make(self):
         x, p0 = self.first.make()
-        p0 = dict(p0, scale=None if p0["scale"] is None else torch.ones_like(p0["scale"]), shift=torch.zeros_like(p0["shift"]))
-        _, p1 = self.second.make()
+        if self.pep == "unit":
+            p0 = dict(p0, scale=None if p0["scale"] is None else torch.ones_like(p0["scale"]), shift=torch.zeros_like(p0["shift"]))
+        elif self.pep == "null":
+            p0 = dict(p0, scale=None, shift=None)
+        else:
+            g = torch.Generator().manual_seed(self.first.seed + 31)
+            co = self.first.layer.cout
+            p0 = dict(p0, scale=torch.randint(1, 3, (co,), generator=g).float(), shift=torch.randint(-4, 9, (co,), generator=g).float())
+        _, p1 = dataclasses.replace(self.second, B=1).make()      # (the parameters do not depend on the batch; its x is not used)
         return x, [p0, p1]
 
     def intermediate(self, x, p0):
@@ -430,7 +513,48 @@ def _chains():
 
 CHAIN_CASES = _chains()
 
-ALL_CASES = DIRECT_CASES + LINEAR_CASES + BF16_CASES + WINO_CASES + WINO_SHAPE_CASES
+TILE1_WORKGROUPS, TILE1_POSITIONS = 2000, 256      # conv_head_fused: the 64 x 256 tile from 2000 workgroups of it on
+
+
+def tile1_batch(n_out):
+    """smallest batch of a 3D layer over output edge n_out at which the fused launch of a 33 .. 64-cout convolution takes the
+    64 x 256 tile: ceil(B n^3 / 256) >= 2000"""
+    return -(-((TILE1_WORKGROUPS - 1) * TILE1_POSITIONS + 1) // n_out ** 3)
+
+
+def _head_chains():
+    """the fp32 conv + head launch (s3r_api.hip: conv_head_fused), one row per route, each under the head's four epilogue forms and
+    the producer forms null and int.  The head has bn=True so that head_scale is a real vector, and act none: negative sums count.
+    (Its one channel draws its scale from four values: seed 961 gives scale 2 and a non-zero shift at cin 24, 40 and 64)"""
+    net = dict((l.name, (l, n)) for l, n in network())
+    (d3, n3), (d4, n4) = net["d3"], net["d4"]
+    c3 = lambda ci, co: L("t", "conv3d", ci, co, 3, 1, 1)
+    up = lambda ci, co: L("t", "deconv3d", ci, co, 4, 2, 1)
+    head = lambda ci: L("h", "conv3d", ci, 1, 1, 1, 0, True, "none")
+    B1 = tile1_batch(8)
+    rows = [  # (route, first layer's Data, head edge, ChainCase keywords)
+        ("direct-c24-tile2", Data(c3(32, 24), 2, 4, 950), 4, dict(algo=DIRECT)),
+        ("direct-c40-tile7", Data(c3(16, 40), 2, 4, 951), 4, dict(algo=DIRECT)),
+        (f"direct-c40-tile1-B{B1}", Data(L("t", "conv3d", 16, 40, 1, 1, 0), B1, 8, 952), 8, dict(algo=DIRECT)),      # (1 x 1 x 1: a large batch stays cheap)
+        ("transposed-direct", Data(up(32, 24), 2, 4, 953), 8, dict(algo=DIRECT)),
+    ]
+    rows += [(f"dwino2-tile{t}", Data(up(32, 24), 2, 4, 954, "f22x2"), 8,
+              dict(algo=WINO, tile=t, ran=(ONE_AXIS_RAN[t],) if t < 2 else ONE_AXIS_RAN)) for t in (0, 1, 2)]
+    rows += [(f"dwino3-tile{t}", Data(up(16, 40), 2, 8, 955, "f22x3"), 16, dict(algo=WINO, tile=t, ran=three_axis_ran(t))) for t in (6, 7, 8)]
+    rows.append(("d3+d4", Data(d3, 1, n3, 956, xmax=1), n4, {}))
+    out = []
+    for route, first, n_head, kw in rows:
+        for pep in ("null", "int"):
+            for ep in LT.EP_FORMS:
+                out.append(ChainCase(f"{route}+head-p{pep}-h{ep}", first, Data(head(first.layer.cout), first.B, n_head, 961, wmax=2, ep=ep),
+                                     pep=pep, fused=True, **kw))
+    return out
+
+
+HEAD_CHAIN_CASES = _head_chains()
+ALL_CHAIN_CASES = CHAIN_CASES + HEAD_CHAIN_CASES       # (CHAIN_CASES alone: the hand-offs tests/test_alignment_gpu.py runs at skewed pointers)
+
+ALL_CASES = DIRECT_CASES + LINEAR_CASES + BF16_CASES + WINO_CASES + WINO_SHAPE_CASES + EP_CASES + LINEAR_NULL_BIAS
 
 
 def unique_data(cases=None):

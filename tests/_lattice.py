@@ -135,8 +135,15 @@ def wino_gain(kind):
 
 
 # ---------------------------------------------------------------- data
-def lattice_case(layer, B, n_in, seed, form="direct", xmax=2, wmax=1, density=1.0, xdensity=1.0):
-    """x (B, cin, n_in, ...) and {"w", "scale", "shift"} on the lattice of `form`, fp32 on the CPU, seeded"""
+EP_FORMS = ("ss", "0s", "s0", "00")
+
+
+def lattice_case(layer, B, n_in, seed, form="direct", xmax=2, wmax=1, density=1.0, xdensity=1.0, ep="ss"):
+    """x (B, cin, n_in, ...) and {"w", "scale", "shift"} on the lattice of `form`, fp32 on the CPU, seeded.  ep: the epilogue's vector
+    form, (scale, shift) each given `s` or NULL `0` — "ss": what the layer has (a scale where it folds a BatchNorm, and a shift);
+    "0s" / "s0" / "00" drop the scale, the shift or both (None: the test bodies pass a NULL pointer).  x, w and the vectors that
+    remain are the SAME numbers in all four forms (a shift without a scale keeps its integer part only)"""
+    assert ep in EP_FORMS and (layer.bn or ep[0] == "0" or ep == "ss"), (ep, "a given scale needs a layer with bn=True")
     assert layer.act in EXACT_ACTS, f"{layer.act} cannot be exact"
     if layer.act == "leaky_relu":
         s = R.act_param(layer)
@@ -167,9 +174,11 @@ def lattice_case(layer, B, n_in, seed, form="direct", xmax=2, wmax=1, density=1.
     else:
         scale = None
     shift = torch.randint(-8, 33, (layer.cout,), generator=g).float()
+    if ep[0] == "0":
+        scale = None
     if scale is not None:
         shift = shift + (scale < 1).float() * torch.randint(0, 4, (layer.cout,), generator=g).float() * 0.25
-    return x, {"w": w, "scale": scale, "shift": shift}
+    return x, {"w": w, "scale": scale, "shift": None if ep[1] == "0" else shift}
 
 
 def expected(layer, x, p, dtype="fp32"):
@@ -249,7 +258,7 @@ def exactness(layer, x, p, form="direct", dtype="fp32"):
     ref, mag = R.ref64(layer, x, p)
     L = R.lipschitz(layer)
     sc = torch.ones(layer.cout, dtype=torch.float64) if p["scale"] is None else p["scale"].double().abs()
-    sh = p["shift"].double().abs()
+    sh = torch.zeros(layer.cout, dtype=torch.float64) if p["shift"] is None else p["shift"].double().abs()
     # fractional bits per channel: 2 where the scale is < 1 (1/4, 1/2 and the shift's quarters), plus the LeakyReLU slope's
     fc = 2.0 * (sc < 1).double() + (frac_bits(layer, {"scale": None}) if layer.act == "leaky_relu" else 0)
     per_ch = mag.transpose(0, 1).reshape(layer.cout, -1).amax(1).cpu() if layer.op != "linear" else mag.amax(0).cpu()

@@ -93,9 +93,10 @@ def _bc(v, y):
 
 
 def epilogue(layer, t, scale, shift):
+    """y * scale + shift; either vector may be None (include/s3r.h: a NULL scale is 1, a NULL shift is 0)"""
     if scale is not None:
         t = t * _bc(scale.to(t.dtype), t)
-    return t + _bc(shift.to(t.dtype), t)
+    return t if shift is None else t + _bc(shift.to(t.dtype), t)
 
 
 def activate(layer, t):
@@ -140,10 +141,10 @@ def ref64(layer, x, p):
     x64 = x.double()
     w64 = p["w"].double().to(x.device)
     sc = None if p["scale"] is None else p["scale"].double().to(x.device)
-    sh = p["shift"].double().to(x.device)
+    sh = None if p["shift"] is None else p["shift"].double().to(x.device)
     pre = epilogue(layer, linmap(layer, x64, w64), sc, sh)
     mag = linmap(layer, x64.abs(), w64.abs())
-    mag = epilogue(layer, mag, None if sc is None else sc.abs(), sh.abs())
+    mag = epilogue(layer, mag, None if sc is None else sc.abs(), None if sh is None else sh.abs())
     return activate(layer, pre), mag
 
 

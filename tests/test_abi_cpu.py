@@ -143,6 +143,33 @@ def test_split_k_choice_is_batch_invariant(s3r, lib):
     assert split["v6"] and not split["v1"] and not split["d3"]
 
 
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+@pytest.mark.parametrize("null", ["scale", "shift", "both"])
+def test_stem_refuses_a_null_scale_or_shift(s3r, lib, dtype, null):
+    """include/s3r.h makes scale and shift optional (NULL = 1 / 0) and every kernel guards its read — except the three stem kernels,
+    which index both vectors unconditionally: s3r_conv_forward (fp32 and bf16 stem) and s3r_chain_forward (a chain of the stem alone,
+    and stem -> e2, where the stem writes e2's Winograd planes: a third kernel) refuse a NULL host-side with S3R_ERR_INVALID before
+    anything is enqueued.  Argument validation only: the pointers are never dereferenced"""
+    spec = s3r.arch_spec
+    (e1, n1, _), (e2, n2, _) = spec.stage_table("encoder")[:2]
+    ok = C.c_void_p(64)
+    sc, sh = (None if null in ("scale", "both") else ok), (None if null in ("shift", "both") else ok)
+    d = s3r._lib.make_desc(e1, 2, n1, dtype=s3r._lib.DTYPE[dtype])
+    assert lib.s3r_conv_forward(C.byref(d), ok, ok, sc, sh, ok, None, 0, None) == -1
+    assert b"stem needs scale and shift" in lib.s3r_last_error(), lib.s3r_last_error()
+    chains = [[(e1, n1)]] + ([[(e1, n1), (e2, n2)]] if dtype == "fp32" else [])
+    for rows in chains:
+        arr = (s3r._lib.Layer * len(rows))()
+        for i, (l, n) in enumerate(rows):
+            arr[i].desc = s3r._lib.make_desc(l, 2, n, tag=i, dtype=s3r._lib.DTYPE[dtype])
+            arr[i].packed_w, arr[i].scale, arr[i].shift = ok.value, ok.value, ok.value
+        arr[0].scale, arr[0].shift = (sc.value if sc else None), (sh.value if sh else None)
+        assert lib.s3r_chain_workspace_elems(arr, len(rows)) >= 0, lib.s3r_last_error()
+        # (ws_fresh = 0: no zero fill is enqueued in front of the check)
+        assert lib.s3r_chain_forward(arr, len(rows), ok, ok, ok, 1 << 40, 0, None) == -1, (len(rows), lib.s3r_last_error())
+        assert b"stem needs" in lib.s3r_last_error(), lib.s3r_last_error()
+
+
 def test_halo_contract(s3r, lib):
     """The MFMA conv kernels read zero padding from memory: single-layer calls must state a halo."""
     spec = s3r.arch_spec

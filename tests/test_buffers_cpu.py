@@ -11,6 +11,7 @@ import torch
 from tests import _alignment_cases as AC
 from tests import _buffer_cases as BC
 from tests import _guard as G
+from tests import _linear_cases as LC
 from tests import _ref64 as R
 
 
@@ -213,8 +214,11 @@ def test_checker_flags_mutations_conv(case):
 
 
 @pytest.mark.parametrize("shape", [(3, 50, 7), (33, 96, 40), (2, 64, 7), (7, 7, 7), (1, 256, 1), (4, 1, 9), (3, 7, 1), (5, 1024, 6144),
-                                   (70, 4096, 100), (32, 8192, 1024)], ids=lambda s: "x".join(map(str, s)))
+                                   (70, 4096, 100), (32, 8192, 1024)] + [s for s in LC.SWEEP if s[1] <= 8192],
+                         ids=lambda s: "x".join(map(str, s)))
 def test_checker_flags_mutations_linear(s3r, shape):
+    """(the sweep's K = 16384 and 65536 are not here: one term in that many is inside the bound, which grows with K — the reason those
+    shapes are held bit for bit by tests/test_exact_gpu.py; tests/test_exact_cpu.py asserts exactly that for K >= 16384)"""
     B, cin, cout = shape
     _selftest(s3r.arch_spec.Layer("t", "linear", cin, min(cout, 8), 1, 1, 0, False, "none"), 1, "direct", cin)
 

@@ -18,6 +18,7 @@ import pytest
 
 from tests import _abi_bodies as AB
 from tests import _buffer_cases as BC
+from tests import _linear_cases as LC
 
 pytestmark = pytest.mark.gpu
 HALF = AB.HALF
@@ -88,10 +89,24 @@ LIN_SHAPES = [(32, 8192, 1024), (5, 1024, 6144), (33, 96, 40), (3, 50, 7), (70, 
               (7, 7, 7), (1, 256, 1)]
 
 
+# ... and every branch of the launch plan: tests/_linear_cases.py::SWEEP holds the reason for each shape
 @pytest.mark.parametrize("act", ["none", "relu", "sigmoid"])
-@pytest.mark.parametrize("shape", LIN_SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", LIN_SHAPES + LC.SWEEP, ids=lambda s: "x".join(map(str, s)))
 def test_linear_forward(s3r, lib, shape, act):
     AB.linear_forward(s3r, lib, shape, act)
+
+
+@pytest.mark.parametrize("kernel", list(LC.PER_KERNEL))
+def test_linear_forward_null_bias(s3r, lib, kernel):
+    """bias = NULL, once per kernel of the plan that applies it (linear_wgk_kernel, linear_finish_kernel behind the ring and behind
+    the naive kernel, linear_finish4_kernel): guards, poison, the fp64 bound at HALF"""
+    AB.linear_forward(s3r, lib, LC.PER_KERNEL[kernel], "relu", bias=False)
+
+
+@pytest.mark.parametrize("kernel", list(LC.PER_KERNEL))
+def test_linear_descriptor_with_a_scale(s3r, lib, kernel):
+    """the same kernels behind an S3R_OP_LINEAR descriptor with a folded BatchNorm: their scale[o] branch on a real vector"""
+    AB.linear_descriptor(s3r, lib, LC.PER_KERNEL[kernel], "relu")
 
 
 # ---------------------------------------------------------------- Chamfer, IoU, disparity, channels-last hand-off

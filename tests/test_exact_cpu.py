@@ -65,7 +65,7 @@ def _one_channel(layer, p, o):
     w = p["w"]
     w = w[:, o:o + 1] if layer.op.startswith("deconv") else w[o:o + 1]
     return dataclasses.replace(layer, cout=1), {"w": w.clone(), "scale": None if p["scale"] is None else p["scale"][o:o + 1],
-                                                 "shift": p["shift"][o:o + 1]}
+                                                 "shift": None if p["shift"] is None else p["shift"][o:o + 1]}
 
 
 def _term_with_effect(layer, x, p, active):
@@ -94,6 +94,48 @@ def _trunc_bf16(v):
 @pytest.mark.parametrize("d", DATA, ids=[d.id for d in DATA])
 def test_bit_equality_catches_every_mutant(d):
     _mutants_caught(d, *d.make())
+
+
+def _vector_mutants_caught(d, xs, p):
+    """a given scale taken as 1, a given shift taken as 0: each must change an output bit (on an active channel with scale != 1 /
+    shift != 0, or the case could not tell a kernel that ignores the vector)"""
+    want = LT.expected(d.layer, xs, p, "bf16" if d.bf16_out else "fp32")
+    bits = (lambda t: t.view(torch.int16)) if d.bf16_out else (lambda t: t.view(torch.int32))
+    for k, name in (("scale", "scale taken as 1"), ("shift", "shift taken as 0")):
+        if p[k] is not None:
+            got = LT.fp32_layer(d.layer, xs, dict(p, **{k: None}))
+            got = got.to(torch.bfloat16) if d.bf16_out else got
+            assert not torch.equal(bits(got), bits(want)), (name, "not caught")
+
+
+def test_null_forms_hold_the_vectors_they_say():
+    for site, forms in X.EP_GROUPS:
+        for d in forms:
+            _, p = d.make()
+            assert (p["scale"] is None) == (d.ep[0] == "0") and (p["shift"] is None) == (d.ep[1] == "0"), (site, d.ep)
+    for c in X.LINEAR_NULL_BIAS:
+        _, p = c.data.make()
+        assert p["scale"] is None and p["shift"] is None
+
+
+@pytest.mark.parametrize("site,forms", X.EP_GROUPS, ids=[g[0] for g in X.EP_GROUPS])
+def test_epilogue_forms_differ_pairwise_and_see_their_vectors(site, forms):
+    """the four forms of a site share x and w; their expected outputs differ pairwise (a NULL form that reused a sibling's vector would
+    show), and for each given vector the mutants `scale taken as 1` and `shift taken as 0` change an output bit"""
+    assert [d.ep for d in forms] == list(LT.EP_FORMS)
+    made = [d.make() for d in forms]
+    assert all(torch.equal(m[0], made[0][0]) and torch.equal(m[1]["w"], made[0][1]["w"]) for m in made)
+    sc, sh = made[0][1]["scale"], made[0][1]["shift"]
+    assert torch.equal(made[2][1]["scale"], sc) and bool((made[1][1]["shift"] == sh.floor()).all())
+    outs = [LT.expected(d.layer, x, p, "bf16" if d.bf16_out else "fp32") for d, (x, p) in zip(forms, made)]
+    act = outs[0].float().transpose(0, 1).reshape(forms[0].layer.cout, -1) if forms[0].layer.op != "linear" else outs[0].float().t()
+    live = (act != 0).any(1)
+    assert bool((live & (sc != 1) & (sh != 0)).any()), "no active channel with scale != 1 and shift != 0"
+    for i in range(4):
+        for j in range(i):
+            assert not torch.equal(outs[i], outs[j]), (site, forms[i].ep, forms[j].ep)
+    for d, (x, p) in zip(forms, made):
+        _vector_mutants_caught(d, x, p)
 
 
 def _mutants_caught(d, xs, p):
@@ -146,12 +188,31 @@ def test_cost_volume_case(c):
     _mutants_caught(c.data, vol, p)
 
 
-@pytest.mark.parametrize("c", X.CHAIN_CASES, ids=[c.id for c in X.CHAIN_CASES])
+_FIRST = {}
+
+
+def _first_layer(c, x, p0):
+    """(exactness record, intermediate) of a chain's first layer: the same for every case over one (first Data, producer form)"""
+    key = (c.first, c.pep, c.dtype)
+    if key not in _FIRST:
+        _FIRST.clear()
+        _FIRST[key] = (LT.exactness(c.first.layer, x, p0, c.first.form, c.dtype), c.intermediate(x, p0))
+    return _FIRST[key]
+
+
+@pytest.mark.parametrize("c", X.ALL_CHAIN_CASES, ids=[c.id for c in X.ALL_CHAIN_CASES])
 def test_chain_case(c):
     x, (p0, p1) = c.make()
-    assert (p0["scale"] is None or bool((p0["scale"] == 1).all())) and bool((p0["shift"] == 0).all()) and c.first.layer.act == "relu"
-    r0 = LT.exactness(c.first.layer, x, p0, c.first.form, c.dtype)
-    h = c.intermediate(x, p0)
+    assert c.first.layer.act == "relu"
+    if c.pep == "unit":
+        assert (p0["scale"] is None or bool((p0["scale"] == 1).all())) and bool((p0["shift"] == 0).all())
+    elif c.pep == "null":
+        assert p0["scale"] is None and p0["shift"] is None
+    else:         # integers: the intermediate stays on the integer lattice, and the producer's scale is not the identity
+        sc, sh = p0["scale"], p0["shift"]
+        assert bool(((sc == 1) | (sc == 2)).all()) and bool((sc == 2).any()) and bool((sh == sh.round()).all()) and bool((sh != 0).any())
+    r0, h = _first_layer(c, x, p0)
+    assert bool((h == h.round()).all()), "the intermediate left the integer lattice"
     r1 = LT.exactness(c.second.layer, h, p1, c.second.form, c.dtype)
     print(f"\n{c.id}: {r0}\n{r1}")
     # (the intermediate of the bf16 chain is never stored as bf16 data the test reads: no share of ties is asked of it, but it must
@@ -160,6 +221,46 @@ def test_chain_case(c):
     if c.dtype == "bf16":
         assert float(h.abs().max()) <= 256 and torch.equal(h, LT.expected(c.first.layer, x, p0))
     _mutants_caught(dataclasses.replace(c.second, dtype="fp32"), h, p1)
+    _vector_mutants_caught(dataclasses.replace(c.second, dtype="fp32"), h, p1)
+    if c.pep == "int":        # the PRODUCER's vectors inside the fused epilogue: scale taken as 1, shift taken as 0
+        want = LT.expected(c.second.layer, h, p1)
+        for name, q in (("producer scale as 1", dict(p0, scale=None)), ("producer shift as 0", dict(p0, shift=None))):
+            assert not torch.equal(LT.expected(c.second.layer, c.intermediate(x[:2], q), p1), want[:2]), (name, "not caught")
+
+
+def _head_routes():
+    routes = {}
+    for c in X.HEAD_CHAIN_CASES:
+        routes.setdefault((c.first, c.pep, c.algo, c.tile), []).append(c)
+    return list(routes.values())
+
+
+@pytest.mark.parametrize("group", _head_routes(), ids=lambda g: g[0].id.rsplit("-h", 1)[0])
+def test_head_forms_of_a_route_differ_pairwise(group):
+    """a NULL head vector that silently took a sibling's values would give that sibling's output"""
+    assert [c.second.ep for c in group] == list(LT.EP_FORMS)
+    x, (p0, _) = group[0].make()
+    h = group[0].intermediate(x[:2], p0)
+    outs = [LT.expected(c.second.layer, h, c.make()[1][1]) for c in group]
+    for i in range(4):
+        for j in range(i):
+            assert not torch.equal(outs[i], outs[j]), (group[i].id, group[j].id)
+
+
+def test_head_chain_routes_are_the_issues(s3r, lib):
+    """one row per route of conv_head_fused, eight cases each; every pair plans as a chain (that the head rode in the first layer's
+    launch is asserted on the device: no head record); the tile-1 batch is the smallest with 2000 workgroups of 256 positions"""
+    B = X.tile1_batch(8)
+    assert -(-(B * 512) // 256) >= 2000 > -(-((B - 1) * 512) // 256)
+    ids = {c.id.split("+head")[0] for c in X.HEAD_CHAIN_CASES}
+    assert ids == {"direct-c24-tile2", "direct-c40-tile7", f"direct-c40-tile1-B{B}", "transposed-direct", "dwino2-tile0", "dwino2-tile1",
+                   "dwino2-tile2", "dwino3-tile6", "dwino3-tile7", "dwino3-tile8", "d3+d4"} and len(X.HEAD_CHAIN_CASES) == 11 * 8
+    for c in X.HEAD_CHAIN_CASES[::8]:
+        arr = (s3r._lib.Layer * 2)()
+        arr[0].desc = s3r._lib.make_desc(c.first.layer, c.first.B, c.first.n_in, tag=0, algo=c.algo, tile=c.tile)
+        arr[1].desc = s3r._lib.make_desc(c.second.layer, c.first.B, c.second.n_in, tag=1)
+        assert lib.s3r_chain_workspace_elems(arr, 2) >= 0, (c.id, lib.s3r_last_error())      # (0: a fused 1 x 1 x 1 pair needs nothing)
+        assert 33 <= c.first.layer.cout <= 64 or c.first.layer.cout == 24, c.id
 
 
 def test_rounding_mutants_are_what_they_say():

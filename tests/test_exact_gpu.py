@@ -21,7 +21,8 @@ A mismatch is reported as the first differing element with its (b, cout, positio
 difference in lattice units (2^-f): a difference equal to one `w x` product names the tap.
 
 Cases: direct fp32 233 (18 network layers x B 1 / 3, 8 shapes x 8 tiles x 2 gather widths, split-K 1 / 2 / 4 and v5 / v6 / d1 at
-network size under split-K 1 .. 16, the general-layer families), linear 28, bf16 276 under each of the two matrix instructions
+network size under split-K 1 .. 16, the general-layer families), linear 28 + the 14 shapes of the launch plan's sweep x act none /
+ReLU + bias = NULL once per kernel (tests/_linear_cases.py: every branch of linear_wgk_ok / linear_split / launch_linear), bf16 276 under each of the two matrix instructions
 (18 layers x B 1 / 3, the 15 x 16 tile matrix), Winograd 48 (one-axis x 3 launch forms, two-axis tiles 3 / 4 / 5 incl. F(2,4) x F(2,4),
 transposed F(2,2) classes and the three-axis form), Winograd at ragged shapes and at the LDS limits 143 (tests/_exact_cases.py::
 _wino_shapes: the smallest shapes at which each branch of those kernels is taken — edges with n mod 4 = 1, 2, 3 and the dword-gather
@@ -30,6 +31,14 @@ two finish kernels, PL and SUB shrunk by LDS under out_halo 8, a padded plane of
 launch form and AUTO, the profiler record naming the form that ran), the cost volume writing v1's plane sets in both layouts, the
 stem -> e2 hand-off, the bf16 d3 + head fused launch, and four runs that drop ONE term on the device and require the mismatch.  On
 an MI355X every one of them is bit-exact: the tests found no kernel or pack bug.
+
+Epilogue forms (tests/_exact_cases.py::_ep_sites, 116 cases): `scale` and `shift` each given or a NULL POINTER — ss / 0s / s0 / 00 — at
+every kernel that ends in `scale ? scale[m] : 1, shift ? shift[m] : 0`: direct epilogue and split-K finish, residue classes,
+depth-to-space, every Winograd launch form, head_kernel, the four linear kernels behind an S3R_OP_LINEAR descriptor with a folded
+BatchNorm, the bf16 MFMA epilogue, bf16 split-K finish and head_bf16_kernel.  The fp32 conv + head launch (_head_chains, 88 cases): one
+row per route of conv_head_fused (direct tiles 2 / 7 / 1, transposed direct, transposed two-axis tiles 0 / 1 / 2, three-axis tiles
+6 / 7 / 8, d3 + d4) x the head's four forms x a NULL / NULL and an integer producer epilogue; no head record may appear.  All bit-exact
+at first contact on an MI355X.
 
 Past the LDS limits (a padded plane of 130^2, four slices of 66^2) the descriptor is refused by the scratch query and by the forward,
 with the NaN fill of the output and the scratch intact, and the library's own launch form at such a shape is the class-parallel one:
@@ -44,7 +53,9 @@ and Tanh stay there too (transcendental), and the 8-bit stem entry (it scales by
 Wall time on an MI355X: `pytest tests -m gpu` without this file 144 s (1181 tests); this file 6 s (838 tests).  With the shape
 sweep: 8.5 s (984 tests) — summed per-test times of one run, the 838 earlier tests 4.1 s, the 146 new ones 2.1 s, of which the
 library-pick case at edge 60 (B = 2, its fp64 reference included) 1.8 s and the first edge-124 case 0.6 s (it makes the data);
-every other new case is below 0.12 s.
+every other new case is below 0.12 s.  With the epilogue forms, the fused-head chains and the linear sweep (236 more tests): 1252 tests,
+`--durations` of one run of the whole GPU suite: 22 of the new ones take 5 ms or more, 0.67 s together, the slowest 0.07 s (linear
+3 x 4096 x 4065, whose case makes 16.6 M weights) against 1.8 s for the slowest earlier case; the other 214 are below 5 ms each.
 """
 import ctypes as C
 
@@ -54,6 +65,7 @@ import torch
 from tests import _buffer_cases as BC
 from tests import _exact_cases as X
 from tests import _lattice as LT
+from tests import _linear_cases as LC
 from tests._abi_calls import DEV, interior, pad, rc_ok, sync
 
 pytestmark = pytest.mark.gpu
@@ -133,7 +145,7 @@ def run_conv(s3r, lib, c):
     yshape = (c.B,) + ysp + (l.cout,) if cl_out else (c.B, l.cout) + ysp
     sp = tuple(range(1, 1 + nd)) if cl_out else tuple(range(2, 2 + nd))
     sc = None if p["scale"] is None else p["scale"].contiguous()
-    sh = p["shift"].contiguous()
+    sh = None if p["shift"] is None else p["shift"].contiguous()      # (None: a NULL pointer, not a vector of ones / zeros)
     outs = []
     if c.ran:
         s3r.profile_enable(8)
@@ -142,7 +154,7 @@ def run_conv(s3r, lib, c):
             y = torch.full(yshape, float("nan"), dtype=torch.bfloat16 if cl_out else torch.float32, device=DEV)
             scr = torch.full((max(need, 1),), float("nan") if fill == "nan" else 0.0, device=DEV)
             rc = lib.s3r_conv_forward(C.byref(desc), xp.data_ptr(), pk.data_ptr(), sc.data_ptr() if sc is not None else None,
-                                      sh.data_ptr(), y.data_ptr(), scr.data_ptr(), need, None)
+                                      sh.data_ptr() if sh is not None else None, y.data_ptr(), scr.data_ptr(), need, None)
             sync()
             if c.refused:                             # bf16: the forced tile is refused when the launch is resolved, before any kernel
                 assert rc < 0 and lib.s3r_last_error() and bool(torch.isnan(y).all()), (c.id, "expected to be refused", rc)
@@ -176,19 +188,24 @@ def test_direct_fp32(s3r, lib, case):
 
 
 # ---------------------------------------------------------------- linear
-@pytest.mark.parametrize("case", X.LINEAR_CASES, ids=[c.id for c in X.LINEAR_CASES])
+LINEAR_RUNS = X.LINEAR_CASES + X.LINEAR_NULL_BIAS
+
+
+@pytest.mark.parametrize("case", LINEAR_RUNS, ids=[c.id for c in LINEAR_RUNS])
 def test_linear(s3r, lib, case):
+    """s3r_linear_forward: the shapes the suite began with, the point head, every branch of the launch plan (tests/_linear_cases.py)
+    and, once per kernel of the plan, bias = NULL"""
     l, B = case.layer, case.B
     x, p, want = _data(case.data)
     need = lib.s3r_linear_scratch_elems(B, l.cin, l.cout)
     assert need >= 0, lib.s3r_last_error()
-    w, b = p["w"].contiguous(), p["shift"].contiguous()
+    w, b = p["w"].contiguous(), None if p["shift"] is None else p["shift"].contiguous()
     outs = []
     for fill in (("nan", "zero") if case.twice else ("nan",)):
         y = torch.full((B, l.cout), float("nan"), device=DEV)
         scr = torch.full((max(need, 1),), float("nan") if fill == "nan" else 0.0, device=DEV)
-        rc_ok(lib, lib.s3r_linear_forward(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), B, l.cin, l.cout, s3r._lib.ACT[l.act],
-                                          scr.data_ptr(), need, None), case.id)
+        rc_ok(lib, lib.s3r_linear_forward(x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(), B, l.cin,
+                                          l.cout, s3r._lib.ACT[l.act], scr.data_ptr(), need, None), case.id)
         sync()
         outs.append(y)
     if len(outs) == 2:
@@ -216,6 +233,19 @@ def test_winograd_shapes(s3r, lib, case):
         cus = torch.cuda.get_device_properties(0).multi_processor_count
         assert X.serial_workgroups(case.layer, case.n_in, case.B) > cus, ("raise B of the dual case: this device has", cus, "compute units")
         assert case.ran == ("winograd-dual",)
+    _check_conv(s3r, lib, case)
+
+
+# ---------------------------------------------------------------- every epilogue site under the four vector forms
+@pytest.mark.parametrize("case", X.EP_CASES, ids=[c.id for c in X.EP_CASES])
+def test_epilogue_forms(s3r, lib, case, monkeypatch):
+    """tests/_exact_cases.py::_ep_sites: scale and shift each given or NULL (a NULL POINTER) at every kernel that ends in
+    `scale ? scale[m] : 1, shift ? shift[m] : 0`; the linear sites through an S3R_OP_LINEAR descriptor, the one route with a scale"""
+    if case.dtype == "bf16":
+        monkeypatch.setenv("S3R_BF16_MFMA", "32" if case.data.ep in ("ss", "00") else "16")      # (both matrix instructions over the forms)
+    if case.layer.op == "linear":
+        desc = make_desc(s3r, case)[1]
+        assert lib.s3r_conv_scratch_elems(C.byref(desc)) == LC.plan(case.B, case.layer.cin, case.layer.cout).scratch
     _check_conv(s3r, lib, case)
 
 
@@ -314,13 +344,26 @@ def test_cost_volume_planes_feed_v1(s3r, lib, case):
     assert_bits(outs[0], want, case.data, p, case.id)
 
 
-CHAIN_RUNS = [(c, m) for c in X.CHAIN_CASES for m in ((32, 16) if c.dtype == "bf16" else (None,))]
+_INTER = {}
+
+
+def _intermediate(case, x, p0):
+    """the first layer's exact output, kept for the cases that share (first Data, producer form)"""
+    key = (case.first, case.pep, case.dtype)
+    if key not in _INTER:
+        _INTER.clear()
+        _INTER[key] = case.intermediate(x, p0)
+    return _INTER[key]
+
+
+CHAIN_RUNS = [(c, m) for c in X.ALL_CHAIN_CASES for m in ((32, 16) if c.dtype == "bf16" else (None,))]
 
 
 @pytest.mark.parametrize("case,mfma", CHAIN_RUNS, ids=[c.id + (f"-mfma{m}" if m else "") for c, m in CHAIN_RUNS])
 def test_chain_handoff(s3r, lib, case, mfma, monkeypatch):
     """two layers through s3r_chain_forward: the stem writing e2's transformed planes; bf16 d3 with the head fused into its launch
-    (under both matrix instructions)"""
+    (under both matrix instructions); every route of the fp32 conv + head launch (tests/_exact_cases.py::_head_chains) under the
+    head's four epilogue forms and a NULL / NULL and an integer producer epilogue"""
     bf = case.dtype == "bf16"
     if mfma:
         monkeypatch.setenv("S3R_BF16_MFMA", str(mfma))
@@ -328,29 +371,30 @@ def test_chain_handoff(s3r, lib, case, mfma, monkeypatch):
     x = x.to(DEV)
     ps = [{k: None if v is None else v.to(DEV).contiguous() for k, v in p.items()} for p in ps]
     parts = (case.first, case.second)
-    want = LT.expected(case.second.layer, case.intermediate(x, ps[0]), ps[1])       # (both chains end in fp32)
+    want = LT.expected(case.second.layer, _intermediate(case, x, ps[0]), ps[1])       # (every chain here ends in fp32)
     B = case.first.B
     arr = (s3r._lib.Layer * 2)()
     keep = []
     for i, (d, p) in enumerate(zip(parts, ps)):
-        desc = s3r._lib.make_desc(d.layer, B, d.n_in, tag=i, dtype=s3r._lib.DTYPE[case.dtype])
+        desc = s3r._lib.make_desc(d.layer, B, d.n_in, tag=i, dtype=s3r._lib.DTYPE[case.dtype], algo=0 if i else case.algo,
+                                  tile=-1 if i else case.tile)
         npk = C.c_int64(0)
         rc_ok(lib, lib.s3r_conv_packed_elems(C.byref(desc), C.byref(npk)), "packed_elems")
         pk = torch.full((npk.value,), float("nan"), device=DEV)
         rc_ok(lib, lib.s3r_conv_pack_weights(C.byref(desc), p["w"].data_ptr(), pk.data_ptr(), None), "pack_weights")
         arr[i].desc, arr[i].packed_w = desc, pk.data_ptr()
         arr[i].scale = p["scale"].data_ptr() if p["scale"] is not None else None
-        arr[i].shift = p["shift"].data_ptr()
+        arr[i].shift = p["shift"].data_ptr() if p["shift"] is not None else None
         keep.append(pk)
     need = lib.s3r_chain_workspace_elems(arr, 2)
-    assert need > 0, lib.s3r_last_error()
+    assert need > 0 or (need == 0 and case.fused), lib.s3r_last_error()      # (a fused pair over an unpadded input needs no workspace)
     xin = x.to(torch.bfloat16).permute(0, *range(2, x.dim()), 1).contiguous() if bf else x.contiguous()
     outs = []
     s3r.profile_enable(16)
     try:
         for fill in ("nan", "zero"):
             y = torch.full(want.shape, float("nan"), device=DEV)
-            ws = torch.full((need,), float("nan") if fill == "nan" else 0.0, device=DEV)
+            ws = torch.full((max(need, 1),), float("nan") if fill == "nan" else 0.0, device=DEV)
             rc_ok(lib, lib.s3r_chain_forward(arr, 2, xin.data_ptr(), y.data_ptr(), ws.data_ptr(), need, 1, None), case.id)
             sync()
             outs.append(y)
@@ -358,7 +402,11 @@ def test_chain_handoff(s3r, lib, case, mfma, monkeypatch):
     finally:
         s3r.profile_enable(0)
     assert torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)), "the result depends on the workspace contents"
-    if bf:            # the hand-off under test is the one that ran: the head inside d3's launch; e2 on a Winograd form
+    if case.fused:    # the head rode in the first layer's launch, on the forced form
+        first = [r for r in rec if r["family"] == "conv_mfma" and r["tag"] == 0]
+        assert not [r for r in rec if r["family"] == "head"] and len(first) == 2, rec
+        assert not case.ran or all(r["ran"] in case.ran for r in first), (case.ran, first)
+    elif bf:          # the hand-off under test is the one that ran: the head inside d3's launch; e2 on a Winograd form
         assert not [r for r in rec if r["family"] == "head"] and [r for r in rec if r["family"] == "conv_mfma" and r["tag"] == 0], rec
     else:
         assert [r for r in rec if r["family"] == "conv_mfma" and r["tag"] == 1 and r["ran"].startswith("winograd")], rec
