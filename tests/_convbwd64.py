@@ -246,6 +246,19 @@ def tail_slice_mask(c):
     return m.reshape((g.mc,) * c.nd)
 
 
+def slice_index(c):
+    """int (mc,)*nd: the K slice (0 .. nsl - 1) whose chunks cover each coarse position of a sample (geo()'s chunk walk)"""
+    g = geo(c)
+    m = np.zeros((g.nrows, g.mc), np.int64)
+    for ch in range(g.nchunks):
+        if g.nseg == 1:
+            m[ch * g.R:(ch + 1) * g.R] = ch // g.cps
+        else:
+            row, w0 = ch // g.nseg, (ch % g.nseg) * g.WL
+            m[row, w0:w0 + g.WL] = ch // g.cps
+    return m.reshape((g.mc,) * c.nd)
+
+
 def nan_taps(c, pos):
     """bool (k,)*nd: the taps t for which, on every axis, pos + p - t is a multiple of s whose quotient lies in [0, mc) — the terms
     A[b][a][q] F[b][f][q s - p + t] of the header's formula that read the fine position `pos`"""

@@ -133,9 +133,11 @@ def _direct_fp32():
         algo = DIRECT if BC.has_wino(dataclasses.replace(c, layer=l)) else c.algo
         cases.append(XCase("g-" + c.id, Data(l, c.B, c.n_in, 400), tile=c.tile, ksplit=c.ksplit, algo=algo, in_halo=c.in_halo,
                            out_halo=c.out_halo))
-    # LeakyReLU: slope 1/2 fused in the split-K finish, slope 2 (> 1: the separate pass) behind a direct and a staged layer
+    # LeakyReLU: slope 1/2 fused in the split-K finish and in the direct kernel's own epilogue, slope 2 (> 1: the separate pass) behind a direct and a staged layer
     cases += [
         XCase("leaky-half-splitk2-finish", Data(L("t", "conv3d", 64, 32, 3, 2, 1, True, "leaky_relu", 1, 0, 0.5), 2, 9, 410), ksplit=2, twice=True),
+        XCase("leaky-half-fused-epilogue", Data(L("t", "conv3d", 32, 32, 3, 1, 1, True, "leaky_relu", 1, 0, 0.5), 2, 8, 413), ksplit=1, algo=DIRECT,
+              twice=True),
         XCase("leaky-2-pass-conv3d", Data(L("t", "conv3d", 32, 32, 3, 1, 1, True, "leaky_relu", 1, 0, 2.0), 2, 8, 411), algo=DIRECT, twice=True),
         XCase("leaky-2-pass-staged-conv2d", Data(L("t", "conv2d", 20, 33, 5, 1, 2, True, "leaky_relu", 1, 0, 2.0), 2, 9, 412), twice=True),
     ]
@@ -525,7 +527,9 @@ def tile1_batch(n_out):
 def _head_chains():
     """the fp32 conv + head launch (s3r_api.hip: conv_head_fused), one row per route, each under the head's four epilogue forms and
     the producer forms null and int.  The head has bn=True so that head_scale is a real vector, and act none: negative sums count.
-    (Its one channel draws its scale from four values: seed 961 gives scale 2 and a non-zero shift at cin 24, 40 and 64)"""
+    (Its one channel draws its scale from four values: seed 997 gives scale 2, a non-zero shift and non-zero weights on the first and the
+    last input channel at cin 24, 40 and 64 — with seed 961 the last weight at cin 40 was 0, and a head that skipped its last channel passed;
+    tests/test_exact_cpu.py keeps the condition)"""
     net = dict((l.name, (l, n)) for l, n in network())
     (d3, n3), (d4, n4) = net["d3"], net["d4"]
     c3 = lambda ci, co: L("t", "conv3d", ci, co, 3, 1, 1)
@@ -546,7 +550,7 @@ def _head_chains():
     for route, first, n_head, kw in rows:
         for pep in ("null", "int"):
             for ep in LT.EP_FORMS:
-                out.append(ChainCase(f"{route}+head-p{pep}-h{ep}", first, Data(head(first.layer.cout), first.B, n_head, 961, wmax=2, ep=ep),
+                out.append(ChainCase(f"{route}+head-p{pep}-h{ep}", first, Data(head(first.layer.cout), first.B, n_head, 997, wmax=2, ep=ep),
                                      pep=pep, fused=True, **kw))
     return out
 

@@ -151,6 +151,26 @@ def test_integer_lattice_is_exact(s3r, lib, r):
     assert np.abs(ref).max() > 0
 
 
+@pytest.mark.parametrize("c", [R.SHAPES[3], R.CASES[3]._replace(B=1, n=41)], ids=R.case_id)
+def test_k_slices_are_added_in_ascending_order(s3r, lib, c):
+    """grad_w[i] of a sample is (((slab 0 + slab 1) + slab 2) + ...) (csrc/s3r_conv_bwd.hip, convbwd_finish_kernel).  One coarse position in
+    each of the first three K slices carries grad_y = 2^15, -2^15, 2^-10 in every channel and x is 2^15 everywhere, so every slab holds ONE
+    non-zero term per element (exact whatever the order inside a slab): 2^30, -2^30 and 32.  In the defined order the sum is
+    (2^30 - 2^30) + 32 = 32, the float64 value; an order that meets 32 while +-2^30 is still in the accumulator loses it (ulp(2^30) = 128)."""
+    sl = R.slice_index(c)
+    assert R.geo(c).nsl >= 3 and c.op == "conv" and c.B == 1
+    o = R.out_edge(c)
+    gy = np.zeros(R.y_shape(c), np.float32)
+    for i, v in enumerate((2.0 ** 15, -2.0 ** 15, 2.0 ** -10)):
+        inner = np.argwhere((sl == i) & np.pad(np.ones((o - 2,) * c.nd, bool), 1))       # (off the edge: every tap meets the grid, asserted below)
+        gy[(0, slice(None)) + tuple(inner[len(inner) // 2])] = v
+    x = np.full(R.x_shape(c), 2.0 ** 15, np.float32)
+    ref, _, _ = R.grad_w64(c, x, gy)
+    assert (ref == 32.0).all()
+    _, gw, _ = run(s3r, lib, c, "none", x, None, gy, None, need=(False, True, False))
+    assert np.array_equal(gw.astype(np.float64), ref), (np.unique(gw), "the K slices were not added in ascending order")
+
+
 @pytest.mark.parametrize("c", [R.D3[0], R.CASES[1]], ids=R.case_id)
 def test_no_activation_and_no_scale_reads_grad_y_itself(s3r, lib, c):
     """act none, scale NULL: gs IS grad_y, and with gs NULL the weight-gradient GEMM reads grad_y directly (no prep pass, nothing of gs in

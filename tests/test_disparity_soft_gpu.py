@@ -89,8 +89,44 @@ def test_hot_limit_is_the_middle_of_the_range(s3r, shape):
     assert ((dr.cpu() - (nr - 1) / 2).abs() <= 1e-3).all()
 
 
+GAPS = [87.0, 87.5, 95.0, 103.0, 103.5, 104.0]      # exp(-gap): 1.6e-38 (kept), 9.9e-39 .. 1.4e-45 (subnormal), 0 in fp32
+
+
+@pytest.mark.parametrize("size", [None, (11, 9)], ids=["feature", "11x9"])
+def test_a_weight_below_flt_min_counts_as_zero(s3r, size):
+    """The kernel's rule `e < FLT_MIN -> 0` (csrc/s3r_disparity.hip): row h has features g_h w in both views and tau = 1, so every
+    pixel's best disparity is 0 with cost 0 and disparity d costs exactly g_h d.  Where exp(-g_h) is below FLT_MIN the float64
+    soft-argmin WITH the rule is exactly 0 and the confidence exactly 1 — a kernel without the rule leaves the subnormal residue
+    sum_d d e_d there; where it is above (g = 87) the far weight stays, within the float64 value's 1e-5."""
+    H, W, D = len(GAPS), 6, 6
+    g = np.array(GAPS, np.float32)[:, None] * np.arange(W, dtype=np.float32)[None, :]          # exact products
+    fl = torch.from_numpy(np.broadcast_to(g, (2, 1, H, W)).copy())
+    kw = {} if size is None else {"out_size": size}
+    dl, dr, cl, cr = (t.cpu().double().numpy() for t in s3r.disparity_soft(fl.to(DEV), fl.clone().to(DEV), D, 1.0, confidence=True, **kw))
+    want_d, want_c = [], []
+    for right in (False, True):
+        c = R.costs(fl.numpy(), fl.numpy(), D, right).astype(np.float64)
+        e = np.exp(c.min(-1, keepdims=True) - c)
+        e[e < np.finfo(np.float32).tiny] = 0.0                                                 # the rule
+        want_d.append((e * np.arange(D)).sum(-1) / e.sum(-1))
+        want_c.append(1.0 / e.sum(-1))
+    assert (want_d[0][:, 1:, 1:] == 0).all() and (want_d[0][:, 0, 1:] > 0).all()                # rows 1.. are the flushed ones
+    if size is None:
+        for got, want in ((dl, want_d[0]), (dr, want_d[1])):
+            assert (got[:, 1:] == 0).all(), got[0, 1:]
+            assert (np.abs(got[:, 0] - want[:, 0]) <= 1e-5 * want[:, 0]).all(), (got[0, 0], want[0, 0])
+        for got, want in ((cl, want_c[0]), (cr, want_c[1])):
+            assert (got == 1).all() and (want == 1).all()
+    else:
+        # output rows that interpolate between flushed feature rows only (source row >= 1 on both sides): exact zeros again
+        src = (np.arange(size[0], dtype=np.float32) + np.float32(0.5)) * (np.float32(H) / np.float32(size[0])) - np.float32(0.5)
+        rows = np.floor(np.maximum(src, 0)) >= 1
+        assert rows.sum() >= size[0] // 2
+        assert (dl[:, rows] == 0).all() and (dr[:, rows] == 0).all() and (cl == 1).all() and (cr == 1).all()
+
+
 # ---------------------------------------------------------------- 3. upsampling
-UPS = [((2, 32, 28, 28, 28), (224, 224), 8.0), ((3, 5, 7, 13, 4), (37, 100), 2.5), ((2, 8, 9, 9, 5), (9, 9), 8.0),
+UPS =[((2, 32, 28, 28, 28), (224, 224), 8.0), ((3, 5, 7, 13, 4), (37, 100), 2.5), ((2, 8, 9, 9, 5), (9, 9), 8.0),
        ((1, 16, 12, 40, 40), (5, 17), 1.0)]
 
 

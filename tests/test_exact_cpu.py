@@ -247,6 +247,22 @@ def test_head_forms_of_a_route_differ_pairwise(group):
             assert not torch.equal(outs[i], outs[j]), (group[i].id, group[j].id)
 
 
+@pytest.mark.parametrize("group", _head_routes()[::2], ids=lambda g: g[0].id.rsplit("+head", 1)[0])
+def test_head_weighs_its_first_and_last_channel_and_dropping_either_is_a_mismatch(group):
+    """a fused head that skipped its last (or first) input channel passes wherever that channel's weight is 0 (tests/mutants/table.py:
+    dwino3_head_last_channel did, on the head data this suite had before)"""
+    c = group[0]
+    x, (p0, p1) = c.make()
+    w = p1["w"].reshape(-1)
+    assert w[0] != 0 and w[-1] != 0, (c.id, w[0], w[-1])
+    h = c.intermediate(x[:2], p0)
+    want = LT.expected(c.second.layer, h, p1)
+    for drop in (0, -1):
+        wd = p1["w"].clone() if hasattr(p1["w"], "clone") else p1["w"].copy()
+        wd.reshape(-1)[drop] = 0
+        assert not torch.equal(LT.expected(c.second.layer, h, dict(p1, w=wd)), want), (c.id, drop)
+
+
 def test_head_chain_routes_are_the_issues(s3r, lib):
     """one row per route of conv_head_fused, eight cases each; every pair plans as a chain (that the head rode in the first layer's
     launch is asserted on the device: no head record); the tile-1 batch is the smallest with 2000 workgroups of 256 positions"""
