@@ -45,6 +45,9 @@
  *                                           feature maps: what `python3 runner.py` runs behind a disparity loss (README.md:75-76)
  *   s3r_disparity_loss_forward / _backward  torch.nn.SmoothL1Loss on the pixels with a valid ground truth (the disp_%02d_{l,r}.exr maps
  *                                           mark background as inf or negative) and its backward, fixed summation order (README.md:75-76)
+ *   s3r_optim_step (+ s3r_optim_state_init, torch.optim.SGD / Adam / AdamW's step and torch.nn.utils.clip_grad_norm_: the parameter update
+ *   s3r_optim_set_lr, its scratch query)    of `python3 runner.py` (training), with a defined rounding order and its step count, powers
+ *                                           and learning rate on the device                (README.md:36,77)
  *
  * Conventions
  *   - every tensor is fp32, contiguous, NCHW / NCDHW, resident in device memory owned by the caller;
@@ -86,7 +89,8 @@ extern "C" {
  * s3r_voxel_bce_backward and s3r_head_backward (+ its scratch query) likewise; s3r_conv_adjoint_desc and s3r_conv_backward (+ its scratch
  * query) likewise; s3r_cost_volume_backward likewise; s3r_batchnorm_train_forward and s3r_batchnorm_train_backward (+ their scratch queries)
  * likewise; s3r_stem_backward (+ its scratch query) likewise; s3r_disparity_soft_backward, s3r_disparity_loss_forward and
- * s3r_disparity_loss_backward likewise: new entry points only, the version stays 8. */
+ * s3r_disparity_loss_backward likewise; s3r_optim_step, s3r_optim_state_init, s3r_optim_set_lr and s3r_optim_scratch_elems (with their two
+ * structs) likewise: new entry points only, the version stays 8. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -786,6 +790,107 @@ int s3r_disparity_loss_forward(const float* pred, const float* gt, float beta, f
  * Profiler: ONE record of family 9, tag 6; `bytes` = pred, gt, grad_pred and grad_scale. */
 int s3r_disparity_loss_backward(const float* pred, const float* gt, const float* grad_scale, float beta, float* grad_pred, int batch,
                                 int64_t pixels, void* hip_stream);
+
+/* The optimizer step: SGD (momentum, Nesterov, L2 decay) and Adam / AdamW over a LIST of fp32 tensors, with an optional global gradient
+ * norm in a fixed order (clip to max_norm; skip the step on a non-finite norm).  Deterministic, atomics-free, nothing read on the host.
+ *
+ * Host array.  `t` (n_tensors entries) is read during the call only.  Its pointers and sizes travel to the device BY VALUE in kernel
+ * arguments, at most S3R_OPTIM_TENSORS_PER_LAUNCH tensors per launch; there is no pointer table in device memory, so nothing the device
+ * dereferences can go stale, and a captured call replays as long as the tensors stay where they were.  1 <= n_tensors <=
+ * S3R_OPTIM_MAX_TENSORS; more than S3R_OPTIM_TENSORS_PER_LAUNCH tensors means more launches of the same kernels.
+ *
+ * Device state.  `state` is S3R_OPTIM_STATE_DWORDS = 8 dwords of device memory, written by s3r_optim_state_init:
+ *   0 step (int32)   1 beta1_pow   2 beta2_pow   3 lr   4 grad_norm (written)   5 clip_coef (written)   6 skipped (int32 count)   7 reserved
+ * lr, the step count and the two running powers live ON THE DEVICE: a replayed graph advances its own bias correction and follows a
+ * learning-rate schedule written into state[3] between replays (s3r_optim_set_lr, or any 4-byte copy).  A step that is not skipped does
+ * step = step + 1 and, for Adam, beta1_pow = beta1_pow * beta1 and beta2_pow = beta2_pow * beta2 — ONE rounded fp32 multiplication per
+ * step, no powf (its result is not correctly rounded and could not be restated bit for bit) — BEFORE the update reads them.
+ * beta1, beta2, eps, weight_decay, max_norm, kind and flags are BAKED at enqueue time: a captured call replays with the values it was
+ * captured with.  s3r_optim_state_init writes step 0, both powers 1.f, lr, grad_norm 0.f, clip_coef 1.f, skipped 0, reserved 0.
+ *
+ * Arithmetic.  Everything is fp32, every operation is rounded on its own (nothing contracted into a fused multiply-add), division and
+ * sqrtf are the correctly rounded IEEE ones, denormals are kept.  Per element, one rounded operation per statement, with p the
+ * parameter, g the gradient as read (grad is never written), mu = beta1 for SGD:
+ *   with S3R_OPT_CLIP, first:      g = g * clip_coef
+ *   S3R_OPT_SGD
+ *     weight_decay != 0:           t = weight_decay * p;  g = g + t
+ *     mu != 0, the first step:     m = g                                        (step == 1 after the advance: as torch, not mu * 0 + g)
+ *     mu != 0, later steps:        a = mu * m;  m = a + g
+ *     mu != 0, S3R_OPT_NESTEROV:   t = mu * m;  g = g + t;      without it: g = m
+ *     then:                        t = lr * g;  p = p - t
+ *     (mu == 0: m is neither read nor written and may be NULL; v is never touched by SGD)
+ *   S3R_OPT_ADAM
+ *     weight_decay != 0, coupled (L2, torch.optim.Adam):                t = weight_decay * p;  g = g + t
+ *     weight_decay != 0, S3R_OPT_DECOUPLED_DECAY (torch.optim.AdamW):   w = lr * weight_decay;  s = w * p;  p = p - s
+ *     a = beta1 * m;  b = (1.f - beta1) * g;  m = a + b
+ *     a = beta2 * v;  q = g * g;  b = (1.f - beta2) * q;  v = a + b
+ *     mh = m / (1.f - beta1_pow);  vh = v / (1.f - beta2_pow);  r = sqrtf(vh);  d = r + eps;  u = mh / d
+ *     t = lr * u;  p = p - t
+ * weight_decay == 0 skips its statements (it is not a multiplication by zero).  Elementwise: bit for bit against a restatement
+ * (tests/_optim64.py), the same bits on every run and at every 4-byte-aligned address.  Without the norm, a NaN gradient propagates
+ * through exactly this arithmetic and poisons only its own element (that it is a NaN is promised; its sign and payload are not).
+ *
+ * Gradient norm, only with S3R_OPT_CLIP or S3R_OPT_SKIP_NONFINITE: the order of s3r_head_backward's sums with a tensor in place of a row.
+ * Each tensor is cut into chunks of 512 consecutive elements (the last may be short: missing elements count as +0.0); within a chunk lane
+ * L (0..63) owns the eight elements 256 j + 4 L + i (j = 0, 1; i = 0..3) and adds its g * g (the product rounded, then added) in ascending
+ * element order to a partial that starts as +0.0; the 64 partials are combined by the halving tree v[L] = v[L] + v[L + o] for L < o,
+ * o = 32, 16, 8, 4, 2, 1.  Each tensor's chunk sums are added in ascending chunk order into a partial that starts as its chunk 0's sum; the
+ * tensor totals are added in ascending tensor order into ONE accumulator that starts as tensor 0's.  grad_norm = sqrtf(total).  With
+ * S3R_OPT_CLIP: d = grad_norm + 1e-6f;  c = max_norm / d;  clip_coef = (c > 1.f) ? 1.f : c (torch's clamp: a NaN stays a NaN and then
+ * poisons every element, as torch.nn.utils.clip_grad_norm_ does); without it clip_coef = 1.f.  Both are written to `state` by every step
+ * that computes the norm, skipped or not; a step without the norm leaves them as they were.  The norm's bits depend on the tensor list
+ * only — not on how it was cut into launches, on `scratch`'s contents on entry or on any address.  A denormal g * g is kept (it is not
+ * flushed to zero).
+ * With S3R_OPT_SKIP_NONFINITE and a grad_norm that is not finite (NaN or infinity): no parameter, moment, step count, power or lr changes
+ * by a bit; `skipped` grows by one (grad_norm and clip_coef show the offending norm).
+ *
+ * scratch: s3r_optim_scratch_elems(t, n_tensors) floats = sum_i ceil(elems_i / 512) + n_tensors (the chunk sums, and per tensor where
+ * its chunk sums start, written by the device on every call); its contents on entry do not matter.  A step WITHOUT the norm uses no
+ * scratch (it may be NULL); with the norm a shorter (or NULL) one is refused.  The query returns S3R_ERR_INVALID for a list it would refuse.
+ *
+ * Refused with S3R_ERR_INVALID and a message, host-side, before anything is enqueued: a NULL d, t or state; a NULL param or grad; a NULL
+ * m where SGD's momentum or Adam needs it, a NULL v for Adam; elems <= 0 or >= 2^31; n_tensors <= 0 or > S3R_OPTIM_MAX_TENSORS; with the
+ * norm, scratch NULL or scratch_elems below the query; a non-finite hyper-parameter, beta1 or beta2 outside [0, 1), a negative eps,
+ * weight_decay or max_norm; an unknown kind or flag bit, S3R_OPT_NESTEROV without SGD momentum, S3R_OPT_DECOUPLED_DECAY without Adam;
+ * param, m and v ranges of one tensor that overlap, or the same param twice in the list.  Pointers need 4-byte alignment only.
+ * Launches: with the norm, one chunk-sum launch per S3R_OPTIM_TENSORS_PER_LAUNCH tensors; ONE advance launch (one wave: the ordered
+ * totals, norm, coefficient, finite test, step and powers); one update launch per S3R_OPTIM_TENSORS_PER_LAUNCH tensors — three launches
+ * for a list of up to 64 tensors.  Every node is a kernel (no memset, no copy).
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new gradients in the same buffers, the state advancing on the device).
+ * Profiler: no record (the step is meant to be captured, and the event profiler must be off while capturing). */
+#define S3R_OPTIM_TENSORS_PER_LAUNCH 64      /* 64 x (4 pointers + size) + the prefix table fit the 4 KB kernel-argument block */
+#define S3R_OPTIM_MAX_TENSORS 4096
+#define S3R_OPTIM_STATE_DWORDS 8
+#define S3R_OPT_SGD 0
+#define S3R_OPT_ADAM 1
+#define S3R_OPT_DECOUPLED_DECAY 1            /* flags: AdamW's weight decay */
+#define S3R_OPT_NESTEROV 2
+#define S3R_OPT_CLIP 4                       /* scale the gradients by clip_coef = min(max_norm / (grad_norm + 1e-6f), 1) */
+#define S3R_OPT_SKIP_NONFINITE 8             /* skip the step when grad_norm is NaN or infinite */
+typedef struct s3r_optim_tensor {
+    float* param;
+    const float* grad;
+    float* m;          /* SGD: the momentum buffer (NULL when beta1 == 0); Adam: the first moment */
+    float* v;          /* Adam: the second moment; SGD: unused, may be NULL */
+    int64_t elems;
+} s3r_optim_tensor;
+typedef struct s3r_optim_desc {
+    int32_t kind;      /* S3R_OPT_SGD, S3R_OPT_ADAM */
+    int32_t flags;     /* S3R_OPT_DECOUPLED_DECAY | S3R_OPT_NESTEROV | S3R_OPT_CLIP | S3R_OPT_SKIP_NONFINITE */
+    float beta1;       /* SGD: momentum (0 = none; then m may be NULL) */
+    float beta2, eps, weight_decay, max_norm;
+} s3r_optim_desc;
+int64_t s3r_optim_scratch_elems(const s3r_optim_tensor* t, int n_tensors);
+/* Writes the eight dwords of a fresh state (step 0, powers 1.f, lr, grad_norm 0.f, clip_coef 1.f, skipped 0, reserved 0): one kernel
+ * launch on `hip_stream` (the hipStream_t of the Conventions above; capturable).  A NULL state or a non-finite or negative lr is refused
+ * with S3R_ERR_INVALID before anything is enqueued. */
+int s3r_optim_state_init(float* state, float lr, void* hip_stream);
+/* Writes lr into state[3], the learning rate of the steps enqueued behind it: one kernel launch on `hip_stream`, ordered like a step
+ * (between two replays of a captured step it is how a schedule reaches the graph).  Refusals as s3r_optim_state_init. */
+int s3r_optim_set_lr(float* state, float lr, void* hip_stream);
+int s3r_optim_step(const s3r_optim_desc* d, const s3r_optim_tensor* t, int n_tensors, float* state, float* scratch,
+                   int64_t scratch_elems, void* hip_stream);
 
 /* Kernel-level profiler: when enabled, every kernel the library launches is bracketed by HIP events
  * on the launch stream.  s3r_profile_read synchronises those events and returns, per launch, the

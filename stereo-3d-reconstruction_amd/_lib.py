@@ -22,6 +22,9 @@ ABI_VERSION = 8
 CONV_BACKWARD_TAG = 1000000      # S3R_CONV_BACKWARD_TAG: a conv backward's profiler record carries this + the layer's tag
 ALGO_AUTO, ALGO_DIRECT, ALGO_WINOGRAD = 0, 1, 2
 ALGO = {None: 0, "auto": 0, "direct": 1, "winograd": 2, False: 1, True: 2}
+OPT_SGD, OPT_ADAM = 0, 1                            # s3r_optim_desc.kind
+OPT_DECOUPLED_DECAY, OPT_NESTEROV, OPT_CLIP, OPT_SKIP_NONFINITE = 1, 2, 4, 8      # s3r_optim_desc.flags
+OPTIM_TENSORS_PER_LAUNCH, OPTIM_MAX_TENSORS, OPTIM_STATE_DWORDS = 64, 4096, 8
 FORM_CUT, FORM_ONE_LAUNCH, FORM_RING = 1, 2, 4      # s3r_prof_record.launch_form (include/s3r.h)
 RAN = {0: "direct", 1: "winograd-serial", 2: "winograd-class-parallel", 3: "winograd-dual", 4: "winograd-2axis", 5: "winograd-3axis", 6: "winograd-3axis-class-parallel"}
 
@@ -41,6 +44,15 @@ class ProfRecord(C.Structure):
     _fields_ = [("family", C.c_int32), ("tag", C.c_int32), ("ms", C.c_float), ("launches", C.c_int32),
                 ("flops", C.c_double), ("bytes", C.c_double), ("exec_flops", C.c_double), ("algo", C.c_int32),
                 ("launch_form", C.c_int32)]
+
+
+class OptimTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("elems", C.c_int64)]
+
+
+class OptimDesc(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("max_norm", C.c_float)]
 
 
 class S3RError(RuntimeError):
@@ -122,6 +134,10 @@ SIGNATURES = {
     "s3r_disparity_loss_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
                                              C.c_void_p]),
     "s3r_disparity_loss_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
+    "s3r_optim_scratch_elems": (C.c_int64, [C.POINTER(OptimTensor), C.c_int]),
+    "s3r_optim_state_init": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
+    "s3r_optim_set_lr": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
+    "s3r_optim_step": (C.c_int, [C.POINTER(OptimDesc), C.POINTER(OptimTensor), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "s3r_profile_enable": (C.c_int, [C.c_int]),
     "s3r_profile_reset": (C.c_int, []),
     "s3r_profile_detail": (C.c_int, [C.c_int]),

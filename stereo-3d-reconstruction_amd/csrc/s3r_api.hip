@@ -3,9 +3,11 @@
 // heads).  Planning (geometry, kernel policy, sizes, the arena) lives in s3r_plan.hip, the profiler in s3r_prof.hip.  Host code only.
 #include "s3r_host.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 
 using namespace s3rh;
 
@@ -1447,6 +1449,101 @@ int s3r_disparity_loss_backward(const float* pred, const float* gt, const float*
     ProfScope ps(s, F_DISP, 6, 0.0, 4.0 * (3.0 * batch * (double)pixels + batch));
     hipError_t e = s3r::launch_disparity_loss_backward(pred, gt, grad_scale, beta, grad_pred, batch, pixels, s);
     if (e != hipSuccess) return hip_fail(e, "disparity loss backward launch");
+    return S3R_OK;
+}
+
+// ---------------------------------------------------------------- optimizer step (s3r_optim.hip)
+namespace {
+
+bool optim_bad(float x, bool below_one) { return !std::isfinite(x) || x < 0.f || (below_one && x >= 1.f); }
+
+// the list's own checks, shared by the query and the step: pointers are looked at by the step only (`need_m`, `need_v` < 0: the query)
+int optim_list(const s3r_optim_tensor* t, int n_tensors, int need_m, int need_v) {
+    if (!t) return fail(S3R_ERR_INVALID, "optimizer: null tensor list");
+    if (n_tensors <= 0 || n_tensors > S3R_OPTIM_MAX_TENSORS)
+        return fail(S3R_ERR_INVALID, "optimizer: n_tensors = %d must be in [1, %d]", n_tensors, S3R_OPTIM_MAX_TENSORS);
+    for (int i = 0; i < n_tensors; ++i) {
+        if (t[i].elems <= 0 || t[i].elems >= kMaxElems)
+            return fail(S3R_ERR_INVALID, "optimizer: tensor %d has elems = %lld (must be in [1, 2^31))", i, (long long)t[i].elems);
+        if (need_m < 0) continue;
+        if (!t[i].param || !t[i].grad) return fail(S3R_ERR_INVALID, "optimizer: tensor %d has a null param or grad", i);
+        if (need_m && !t[i].m) return fail(S3R_ERR_INVALID, "optimizer: tensor %d has a null m (momentum / first moment)", i);
+        if (need_v && !t[i].v) return fail(S3R_ERR_INVALID, "optimizer: tensor %d has a null v (second moment)", i);
+    }
+    if (s3r::optim_chunks(t, n_tensors) + n_tensors >= kMaxElems) return fail(S3R_ERR_INVALID, "optimizer: the list has 2^31 chunks or more");
+    return S3R_OK;
+}
+
+bool optim_overlap(const float* a, const float* b, int64_t n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, bytes = (uintptr_t)n * 4;
+    return a && b && x < y + bytes && y < x + bytes;
+}
+
+}  // namespace
+
+int64_t s3r_optim_scratch_elems(const s3r_optim_tensor* t, int n_tensors) {
+    int rc = optim_list(t, n_tensors, -1, -1);
+    if (rc) return rc;
+    return s3r::optim_chunks(t, n_tensors) + n_tensors;
+}
+
+int s3r_optim_state_init(float* state, float lr, void* hip_stream) {
+    if (!state) return fail(S3R_ERR_INVALID, "optimizer: null state");
+    if (optim_bad(lr, false)) return fail(S3R_ERR_INVALID, "optimizer: lr must be finite and >= 0");
+    hipError_t e = s3r::launch_optim_state_init(state, lr, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "optimizer state init launch");
+    return S3R_OK;
+}
+
+int s3r_optim_set_lr(float* state, float lr, void* hip_stream) {
+    if (!state) return fail(S3R_ERR_INVALID, "optimizer: null state");
+    if (optim_bad(lr, false)) return fail(S3R_ERR_INVALID, "optimizer: lr must be finite and >= 0");
+    hipError_t e = s3r::launch_optim_set_lr(state, lr, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "optimizer set-lr launch");
+    return S3R_OK;
+}
+
+int s3r_optim_step(const s3r_optim_desc* d, const s3r_optim_tensor* t, int n_tensors, float* state, float* scratch,
+                   int64_t scratch_elems, void* hip_stream) {
+    if (!d) return fail(S3R_ERR_INVALID, "optimizer: null descriptor");
+    if (d->kind != S3R_OPT_SGD && d->kind != S3R_OPT_ADAM) return fail(S3R_ERR_INVALID, "optimizer: unknown kind %d", d->kind);
+    const int known = S3R_OPT_DECOUPLED_DECAY | S3R_OPT_NESTEROV | S3R_OPT_CLIP | S3R_OPT_SKIP_NONFINITE;
+    if (d->flags & ~known) return fail(S3R_ERR_INVALID, "optimizer: unknown flag bits 0x%x", d->flags & ~known);
+    const bool adam = d->kind == S3R_OPT_ADAM;
+    if (optim_bad(d->beta1, true)) return fail(S3R_ERR_INVALID, "optimizer: beta1 (SGD: momentum) must be finite and in [0, 1)");
+    if (adam && optim_bad(d->beta2, true)) return fail(S3R_ERR_INVALID, "optimizer: beta2 must be finite and in [0, 1)");
+    if (adam && optim_bad(d->eps, false)) return fail(S3R_ERR_INVALID, "optimizer: eps must be finite and >= 0");
+    if (optim_bad(d->weight_decay, false)) return fail(S3R_ERR_INVALID, "optimizer: weight_decay must be finite and >= 0");
+    if (optim_bad(d->max_norm, false)) return fail(S3R_ERR_INVALID, "optimizer: max_norm must be finite and >= 0");
+    if ((d->flags & S3R_OPT_NESTEROV) && (adam || d->beta1 == 0.f))
+        return fail(S3R_ERR_INVALID, "optimizer: the nesterov flag needs SGD with momentum");
+    if ((d->flags & S3R_OPT_DECOUPLED_DECAY) && !adam) return fail(S3R_ERR_INVALID, "optimizer: the decoupled-decay flag needs Adam");
+    if (!state) return fail(S3R_ERR_INVALID, "optimizer: null state");
+    const bool need_m = adam || d->beta1 != 0.f;
+    int rc = optim_list(t, n_tensors, need_m, adam);
+    if (rc) return rc;
+    const bool with_norm = (d->flags & (S3R_OPT_CLIP | S3R_OPT_SKIP_NONFINITE)) != 0;
+    if (with_norm) {
+        const int64_t need = s3r::optim_chunks(t, n_tensors) + n_tensors;
+        if (!scratch || scratch_elems < need)
+            return fail(S3R_ERR_INVALID, "optimizer: the gradient norm needs %lld floats of scratch (s3r_optim_scratch_elems), got %lld",
+                        (long long)need, scratch ? (long long)scratch_elems : 0ll);
+    }
+    std::vector<std::pair<uintptr_t, int>> ps((size_t)n_tensors);
+    for (int i = 0; i < n_tensors; ++i) {
+        const float* m = need_m ? t[i].m : nullptr;
+        const float* v = adam ? t[i].v : nullptr;
+        if (optim_overlap(t[i].param, m, t[i].elems) || optim_overlap(t[i].param, v, t[i].elems) || optim_overlap(m, v, t[i].elems))
+            return fail(S3R_ERR_INVALID, "optimizer: tensor %d: param, m and v overlap", i);
+        ps[(size_t)i] = {(uintptr_t)t[i].param, i};
+    }
+    std::sort(ps.begin(), ps.end());
+    for (int i = 1; i < n_tensors; ++i)
+        if (ps[(size_t)i].first == ps[(size_t)i - 1].first)
+            return fail(S3R_ERR_INVALID, "optimizer: tensors %d and %d have the same param", ps[(size_t)i - 1].second, ps[(size_t)i].second);
+    hipError_t e = s3r::launch_optim_step(d->kind, d->flags, d->beta1, d->beta2, d->eps, d->weight_decay, d->max_norm, t, n_tensors, state,
+                                          scratch, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "optimizer step launch");
     return S3R_OK;
 }
 

@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <atomic>
 
+struct s3r_optim_tensor;      // include/s3r.h
+
 namespace s3r {
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device only: remember per (kernel
@@ -383,6 +385,14 @@ hipError_t launch_disparity_loss(const float* pred, const float* gt, float beta,
                                  int64_t P, hipStream_t s);
 hipError_t launch_disparity_loss_backward(const float* pred, const float* gt, const float* gscale, float beta, float* gpred, int B,
                                           int64_t P, hipStream_t s);
+
+// s3r_optim.hip: the optimizer step over a host list of tensors (include/s3r.h, s3r_optim_step): [chunk sums of g * g per 64 tensors] +
+// one advance launch + one update launch per 64 tensors; optim_chunks is the list's chunk count (the scratch query's first term)
+long long optim_chunks(const ::s3r_optim_tensor* t, int n);
+hipError_t launch_optim_state_init(float* state, float lr, hipStream_t s);
+hipError_t launch_optim_set_lr(float* state, float lr, hipStream_t s);
+hipError_t launch_optim_step(int kind, int flags, float beta1, float beta2, float eps, float wd, float max_norm,
+                             const ::s3r_optim_tensor* t, int n_tensors, float* state, float* scratch, hipStream_t s);
 
 #if defined(__HIPCC__)
 // Winograd F(4, 3) input transform along one axis (s3r_conv_wino.hip): the six class values of six consecutive padded rows.
