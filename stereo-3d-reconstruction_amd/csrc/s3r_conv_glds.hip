@@ -649,10 +649,9 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(const ConvParams p, in
     }
 }
 
-static thread_local int g_launch_count = 0;          // kernels launched by the last launch_conv_mfma (split-K finish included)
-int conv_last_launch_count() { return g_launch_count; }
-static thread_local int g_launch_form = 0;           // s3r_prof_record.launch_form of the last launch_conv_mfma: 1 cut, 2 one launch, 4 ring
-int conv_last_launch_form() { return g_launch_form; }
+// the tally of the launch_conv_mfma in progress on this thread, handed out as its ConvLaunchInfo
+static thread_local int g_launch_count = 0;          // kernels launched (split-K finish included)
+static thread_local int g_launch_form = 0;           // s3r_prof_record.launch_form: 1 cut, 2 one launch, 4 ring
 
 hipError_t launch_conv_finish(const ConvParams& p, int npad, hipStream_t stream) {
     g_launch_count += 1;
@@ -927,7 +926,7 @@ static bool plan_tail_cut(const ConvParams& p, int cfg, int* n_cut) {
 }
 
 // code = tile_cfg (15 = heuristic) + 16 * forced_vec (0 = widest legal)
-hipError_t launch_conv_mfma(const ConvParams& pin, int code, hipStream_t stream) {
+static hipError_t conv_mfma_launches(const ConvParams& pin, int code, hipStream_t stream) {
     ConvParams p = pin;
     g_launch_count = 0;
     g_launch_form = 0;
@@ -973,6 +972,13 @@ hipError_t launch_conv_mfma(const ConvParams& pin, int code, hipStream_t stream)
         return launch_tile(p, 3, vec, stream);
     }
     return launch_tile(p, cfg, vec, stream);
+}
+
+hipError_t launch_conv_mfma(const ConvParams& p, int code, hipStream_t stream, ConvLaunchInfo* info) {
+    const hipError_t e = conv_mfma_launches(p, code, stream);
+    info->launches = g_launch_count;
+    info->form = g_launch_form;
+    return e;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // Host-side internals shared by the host translation units of libs3r_hip.so — s3r_prof.hip (event profiler), s3r_plan.hip (layer
-// geometry, kernel policy, sizes, chain / arena planner) and s3r_api.hip (the C-ABI entry points and the runners that enqueue
-// kernels).  Not part of the ABI (include/s3r.h) and not seen by the kernel sources (those share s3r_kernels.h).
+// geometry, kernel policy, sizes, the packed weight image's layout, chain / arena planner) and s3r_api.hip (one runner per kernel
+// path, the dispatcher over them and the C-ABI entry points).  Not part of the ABI (include/s3r.h) and not seen by the kernel
+// sources (those share s3r_kernels.h).
 #pragma once
 #include "../../include/s3r.h"
 #include "s3r_kernels.h"
@@ -34,7 +35,7 @@ struct ProfScope {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int launches = 1;     // kernel launches inside the scope (a conv may be cut into bulk + remainder, + split-K finish)
     int algo = 0;         // what ran: 0 direct, 1 / 2 / 3 the Winograd serial / class-parallel / dual form, 4 the two-axis algorithm
-    int form = 0;         // s3r_prof_record.launch_form: OR of conv_last_launch_form() over the scope's direct launches
+    int form = 0;         // s3r_prof_record.launch_form: OR of ConvLaunchInfo::form over the scope's direct launches
     double exec = -1.0;   // MFMA FLOPs executed (< 0: the algorithmic count)
     int family, prev_tag = 0;
     hipStream_t stream;
@@ -83,7 +84,6 @@ struct Plan {
     int64_t total = 0;
 };
 
-
 int fail(int code, const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 int64_t ipow(int64_t b, int e);
@@ -123,7 +123,16 @@ bool wino_layer(const s3r_conv_desc* d);
 bool dwino_layer(const s3r_conv_desc* d);
 bool dwino3_layer(const s3r_conv_desc* d);
 bool dwino3_desc_ok(const s3r_conv_desc* d);
-int64_t dwino3_w_offset(const s3r_conv_desc* d);
+// The packed image of an fp32 MFMA layer that is not staged, the ONE description packing, sizing and the runners share: convolution
+// [direct | one-axis | two-axis], transposed [direct (8 classes x 8 taps) | two-axis classes | three-axis].  Floats; -1: no such slab
+struct PackedLayout { int64_t direct, wino, dwino, wino2, dwino3, total; };
+PackedLayout packed_layout(const s3r_conv_desc* d, const Geo& g);
+// the divisors of the conv kernels' position decode, from the positions per sample (Nd, Nh, Nw)
+inline void set_divs(s3r::ConvParams& p) {
+    p.dS = s3r::FastDiv((unsigned)(p.Nd * p.Nh * p.Nw));
+    p.dHW = s3r::FastDiv((unsigned)(p.Nh * p.Nw));
+    p.dW = s3r::FastDiv((unsigned)p.Nw);
+}
 struct Dwino3Need { int64_t diff, total; bool split; };
 Dwino3Need dwino3_need(const s3r_conv_desc* d, int form);
 bool wino_desc_ok(const s3r_conv_desc* d);

@@ -189,14 +189,14 @@ struct ConvParamsH {
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };      // (the epilogues'; LeakyReLU / ELU / Tanh run as launch_act behind ACT_NONE)
 
 // launchers (defined in the .hip files); every launcher enqueues on `stream` and returns hipGetLastError()
-hipError_t launch_conv_mfma(const ConvParams& p, int tile_code, hipStream_t stream);   // code = cfg + 16*vec
+// launch_conv_mfma's report, success or not: its kernel launches (split-K finish included), s3r_prof_record.launch_form's bits
+struct ConvLaunchInfo { int launches, form; };
+hipError_t launch_conv_mfma(const ConvParams& p, int tile_code, hipStream_t stream, ConvLaunchInfo* info);   // code = cfg + 16*vec
 int conv_pick_tile(const ConvParams& p);
 int conv_pick_vec(const ConvParams& p);
 int conv_pick_ksplit(const ConvParams& p, int tile_cfg);
 int64_t conv_scratch_elems(const ConvParams& p, int tile_cfg);
 int conv_num_tiles();
-int conv_last_launch_count();     // kernel launches the calling thread's last launch_conv_mfma made
-int conv_last_launch_form();      // and how it sent them out: s3r_prof_record.launch_form's bits (include/s3r.h)
 void conv_tile_dims(int tile_cfg, int* bm, int* bn);
 hipError_t launch_pack_conv(const float* w, float* wp, int Cin, int Cout, int CoutPad, int T, int transposed,
                             hipStream_t s);

@@ -36,7 +36,6 @@ int64_t ipow(int64_t b, int e) {
 // r03 used for them (v3 0.505 -> 0.431 ms, v5 0.304 -> 0.251 alone at B = 32): one group size, one class kernel.
 int wino_r(const s3r_conv_desc*) { return 4; }
 
-
 const char* last_error() { return g_err; }
 
 // ---------------------------------------------------------------- layer geometry
@@ -146,6 +145,61 @@ StagedGeo staged_geo(const s3r_conv_desc* d) {
     return s;
 }
 
+// the rules of the transformed layouts, and x_elems / y_elems of a tensor that is a consumer's operand instead of a plain activation
+static int layout_elems(const s3r_conv_desc* d, Geo* g) {
+    if (d->in_layout == S3R_LAYOUT_WINO_H) {     // the four F(2,3)-along-H plane sets a 3 x 3 [x 3] stride-1 pad-1 convolution reads
+        if (d->dtype != S3R_F32 || d->op != S3R_OP_CONV || d->stride != 1 || d->k != 3 || d->pad != 1 || (g->in & 1) || d->in_halo != 1 ||
+            d->cin % 16 != 0 || d->cout <= 1)
+            return fail(S3R_ERR_INVALID, "a Winograd-transformed input serves an fp32 Conv k=3 s=1 p=1 over an even edge, in_halo = 1");
+        if (g->in % wino_r(d) != 0) return fail(S3R_ERR_INVALID, "a Winograd-transformed input needs an edge that is a multiple of %d", wino_r(d));
+        g->x_elems = (wino_r(d) + 2) * (int64_t)d->batch * d->cin * (g->nd == 3 ? g->in_p : 1) * (g->in / wino_r(d)) * g->in_p;
+    }
+    if (d->in_layout == S3R_LAYOUT_WINO_DH) {    // the 36 two-axis plane sets a 3 x 3 x 3 stride-1 pad-1 convolution reads
+        if (d->dtype != S3R_F32 || d->op != S3R_OP_CONV || d->ndim != 3 || d->stride != 1 || d->k != 3 || d->pad != 1 || (g->in & 3) ||
+            d->in_halo != 1 || d->cin % 32 != 0 || d->cout <= 1)
+            return fail(S3R_ERR_INVALID, "a two-axis Winograd-transformed input serves an fp32 Conv3d k=3 s=1 p=1 over an edge %% 4 == 0, in_halo = 1");
+        g->x_elems = 36 * (int64_t)d->batch * d->cin * (g->in / 4) * (g->in / 4) * g->in_p;
+    }
+    if (d->in_layout == S3R_LAYOUT_WINO_HW) {    // the 36 two-axis plane sets of a 2D layer, positions flat
+        if (d->dtype != S3R_F32 || d->op != S3R_OP_CONV || d->ndim != 2 || d->stride != 1 || d->k != 3 || d->pad != 1 || (g->in & 3) ||
+            d->in_halo != 1 || d->cin % 32 != 0 || d->cout <= 1)
+            return fail(S3R_ERR_INVALID, "a two-axis Winograd-transformed input (2D) serves an fp32 Conv2d k=3 s=1 p=1 over an edge %% 4 == 0, in_halo = 1");
+        g->x_elems = 36 * (int64_t)d->cin * s3r::wino2_npad((int64_t)d->batch * (g->in / 4) * (g->in / 4));
+    }
+    if (d->out_layout == S3R_LAYOUT_WINO_HW) {   // ... written by the layer in front of it: the plane sets of THIS layer's halo-1 output
+        if (d->dtype != S3R_F32 || d->op != S3R_OP_CONV || d->ndim != 2 || (g->out & 3) || d->cout % 32 != 0 || d->act == S3R_ACT_SIGMOID)
+            return fail(S3R_ERR_INVALID, "the two-axis Winograd output layout is written by an fp32 Conv2d with an output edge %% 4 == 0 and cout %% 32 == 0");
+        g->y_elems = 36 * (int64_t)d->cout * s3r::wino2_npad((int64_t)d->batch * (g->out / 4) * (g->out / 4));
+    }
+    if (d->in_layout == S3R_LAYOUT_WINO_3D) {    // the plane sets of any 3D two-axis layer, partial last groups included
+        const int ax = wino2_ax(d);
+        if ((ax != 0 && ax != 1) || d->in_halo != d->pad)
+            return fail(S3R_ERR_INVALID, "the general two-axis Winograd input layout serves an fp32 Conv3d k=3 s=1 p=1 / k=4 s=1 p=0 with cin %% %d == 0, "
+                        "in_halo = pad", s3r::wino_bk());
+        g->x_elems = wino2_geo(d).v_sample * d->batch;
+    }
+    if (d->in_layout == S3R_LAYOUT_DIFF) {       // [x | Dh | Dd | Ddh] of the transposed Winograd form
+        if (!dwino_layer(d) || d->in_halo != 1)
+            return fail(S3R_ERR_INVALID, "the difference-tensor input layout serves the Winograd form of an fp32 ConvTranspose3d k=4 s=2 p=1 over an "
+                        "edge %% 4 == 0, in_halo = 1");
+        g->x_elems *= 4;
+    }
+    if (d->out_layout == S3R_LAYOUT_WINO_3D || d->out_layout == S3R_LAYOUT_DIFF) {      // ... written by the layer in front of such a consumer
+        const bool diff = d->out_layout == S3R_LAYOUT_DIFF;
+        if (d->dtype != S3R_F32 || d->ndim != 3 || d->cout % s3r::wino_bk() != 0 || d->act > S3R_ACT_RELU ||
+            (diff ? d->out_halo != 1 || (g->out & 3) : d->out_halo > 1 || g->out < (d->out_halo ? 4 : 5)))
+            return fail(S3R_ERR_INVALID, "a consumer's operand is written by an fp32 3D layer with cout %% %d == 0, no activation or ReLU, and the halo the "
+                        "consumer reads (two-axis planes: out_halo 1 for k3 p1, 0 for k4 p0; difference tensors: out_halo 1, output edge %% 4 == 0)",
+                        s3r::wino_bk());
+        if (diff) g->y_elems *= 4;
+        else {
+            const int sg = d->out_halo ? (g->out + 3) / 4 : (g->out - 2) / 2;
+            g->y_elems = (int64_t)(d->out_halo ? 36 : 25) * d->batch * d->cout * sg * sg * g->out_p;
+        }
+    }
+    return S3R_OK;
+}
+
 int geometry(const s3r_conv_desc* d, Geo* g) {
     if (!d) return fail(S3R_ERR_INVALID, "null descriptor");
     if (d->batch <= 0 || d->cin <= 0 || d->cout <= 0) return fail(S3R_ERR_INVALID, "batch/cin/cout must be positive");
@@ -209,56 +263,8 @@ int geometry(const s3r_conv_desc* d, Geo* g) {
     g->out_sp = ipow(g->out, g->nd);
     g->x_elems = (int64_t)d->batch * d->cin * ipow(g->in_p, g->nd);
     g->y_elems = (int64_t)d->batch * d->cout * ipow(g->out_p, g->nd);
-    if (d->in_layout == S3R_LAYOUT_WINO_H) {     // the four F(2,3)-along-H plane sets a 3 x 3 [x 3] stride-1 pad-1 convolution reads
-        if (d->dtype != S3R_F32 || d->op != S3R_OP_CONV || d->stride != 1 || d->k != 3 || d->pad != 1 || (g->in & 1) || d->in_halo != 1 ||
-            d->cin % 16 != 0 || d->cout <= 1)
-            return fail(S3R_ERR_INVALID, "a Winograd-transformed input serves an fp32 Conv k=3 s=1 p=1 over an even edge, in_halo = 1");
-        if (g->in % wino_r(d) != 0) return fail(S3R_ERR_INVALID, "a Winograd-transformed input needs an edge that is a multiple of %d", wino_r(d));
-        g->x_elems = (wino_r(d) + 2) * (int64_t)d->batch * d->cin * (g->nd == 3 ? g->in_p : 1) * (g->in / wino_r(d)) * g->in_p;
-    }
-    if (d->in_layout == S3R_LAYOUT_WINO_DH) {    // the 36 two-axis plane sets a 3 x 3 x 3 stride-1 pad-1 convolution reads
-        if (d->dtype != S3R_F32 || d->op != S3R_OP_CONV || d->ndim != 3 || d->stride != 1 || d->k != 3 || d->pad != 1 || (g->in & 3) ||
-            d->in_halo != 1 || d->cin % 32 != 0 || d->cout <= 1)
-            return fail(S3R_ERR_INVALID, "a two-axis Winograd-transformed input serves an fp32 Conv3d k=3 s=1 p=1 over an edge %% 4 == 0, in_halo = 1");
-        g->x_elems = 36 * (int64_t)d->batch * d->cin * (g->in / 4) * (g->in / 4) * g->in_p;
-    }
-    if (d->in_layout == S3R_LAYOUT_WINO_HW) {    // the 36 two-axis plane sets of a 2D layer, positions flat
-        if (d->dtype != S3R_F32 || d->op != S3R_OP_CONV || d->ndim != 2 || d->stride != 1 || d->k != 3 || d->pad != 1 || (g->in & 3) ||
-            d->in_halo != 1 || d->cin % 32 != 0 || d->cout <= 1)
-            return fail(S3R_ERR_INVALID, "a two-axis Winograd-transformed input (2D) serves an fp32 Conv2d k=3 s=1 p=1 over an edge %% 4 == 0, in_halo = 1");
-        g->x_elems = 36 * (int64_t)d->cin * s3r::wino2_npad((int64_t)d->batch * (g->in / 4) * (g->in / 4));
-    }
-    if (d->out_layout == S3R_LAYOUT_WINO_HW) {   // ... written by the layer in front of it: the plane sets of THIS layer's halo-1 output
-        if (d->dtype != S3R_F32 || d->op != S3R_OP_CONV || d->ndim != 2 || (g->out & 3) || d->cout % 32 != 0 || d->act == S3R_ACT_SIGMOID)
-            return fail(S3R_ERR_INVALID, "the two-axis Winograd output layout is written by an fp32 Conv2d with an output edge %% 4 == 0 and cout %% 32 == 0");
-        g->y_elems = 36 * (int64_t)d->cout * s3r::wino2_npad((int64_t)d->batch * (g->out / 4) * (g->out / 4));
-    }
-    if (d->in_layout == S3R_LAYOUT_WINO_3D) {    // the plane sets of any 3D two-axis layer, partial last groups included
-        const int ax = wino2_ax(d);
-        if ((ax != 0 && ax != 1) || d->in_halo != d->pad)
-            return fail(S3R_ERR_INVALID, "the general two-axis Winograd input layout serves an fp32 Conv3d k=3 s=1 p=1 / k=4 s=1 p=0 with cin %% %d == 0, "
-                        "in_halo = pad", s3r::wino_bk());
-        g->x_elems = wino2_geo(d).v_sample * d->batch;
-    }
-    if (d->in_layout == S3R_LAYOUT_DIFF) {       // [x | Dh | Dd | Ddh] of the transposed Winograd form
-        if (!dwino_layer(d) || d->in_halo != 1)
-            return fail(S3R_ERR_INVALID, "the difference-tensor input layout serves the Winograd form of an fp32 ConvTranspose3d k=4 s=2 p=1 over an "
-                        "edge %% 4 == 0, in_halo = 1");
-        g->x_elems *= 4;
-    }
-    if (d->out_layout == S3R_LAYOUT_WINO_3D || d->out_layout == S3R_LAYOUT_DIFF) {      // ... written by the layer in front of such a consumer
-        const bool diff = d->out_layout == S3R_LAYOUT_DIFF;
-        if (d->dtype != S3R_F32 || d->ndim != 3 || d->cout % s3r::wino_bk() != 0 || d->act > S3R_ACT_RELU ||
-            (diff ? d->out_halo != 1 || (g->out & 3) : d->out_halo > 1 || g->out < (d->out_halo ? 4 : 5)))
-            return fail(S3R_ERR_INVALID, "a consumer's operand is written by an fp32 3D layer with cout %% %d == 0, no activation or ReLU, and the halo the "
-                        "consumer reads (two-axis planes: out_halo 1 for k3 p1, 0 for k4 p0; difference tensors: out_halo 1, output edge %% 4 == 0)",
-                        s3r::wino_bk());
-        if (diff) g->y_elems *= 4;
-        else {
-            const int sg = d->out_halo ? (g->out + 3) / 4 : (g->out - 2) / 2;
-            g->y_elems = (int64_t)(d->out_halo ? 36 : 25) * d->batch * d->cout * sg * sg * g->out_p;
-        }
-    }
+    const int rc = layout_elems(d, g);
+    if (rc) return rc;
     g->w_elems = (int64_t)d->cin * d->cout * ipow(d->k, g->nd);
     if (d->op == S3R_OP_DECONV)
         g->flops = 2.0 * d->batch * (double)d->cin * g->in_sp * d->cout * ipow(d->k, g->nd);
@@ -276,7 +282,6 @@ int geometry(const s3r_conv_desc* d, Geo* g) {
         return fail(S3R_ERR_INVALID, "tensor too large for one call (>= 2^31 elements / 4 GiB): split the batch");
     return S3R_OK;
 }
-
 
 // which kernel serves a layer shape (halos are checked separately, by check_halos)
 int route(const s3r_conv_desc* d, Route* r) {
@@ -343,7 +348,6 @@ bool dwino3_desc_ok(const s3r_conv_desc* d) {
     return dwino3_layer(d) && d->act < S3R_ACT_SIGMOID && d->in_halo == 1 && d->ksplit <= 1 && d->in_layout == S3R_LAYOUT_PLAIN &&
            d->out_layout == S3R_LAYOUT_PLAIN;
 }
-// its 8 x 27 class slabs sit behind the direct slab and the two-axis form's
 // scratch of the three-axis form: [Dh | Dd | Ddh] then, class-parallel form only, the slabs
 Dwino3Need dwino3_need(const s3r_conv_desc* d, int form) {
     Dwino3Need n;
@@ -354,9 +358,6 @@ Dwino3Need dwino3_need(const s3r_conv_desc* d, int form) {
     // device's compute units, and a size query must not depend on the device it is asked on — ADVICE r05)
     n.total = n.diff + ((n.split || form < 0) ? (s3r::dwino3_slab_elems(d->cout, ntotal) + 255) / 256 * 256 : 0);
     return n;
-}
-int64_t dwino3_w_offset(const s3r_conv_desc* d) {
-    return 64 * (int64_t)d->cin * cout_pad(d->cout) + (dwino_layer(d) ? dwino_w_elems(d) : 0);
 }
 // the descriptor can run its layer's Winograd form
 bool wino_desc_ok(const s3r_conv_desc* d) {
@@ -545,6 +546,15 @@ int wino_bmax(const s3r_conv_desc* d) {
     return (int)(m < d->batch ? m : d->batch);
 }
 int64_t dwino_w_elems(const s3r_conv_desc* d) { return 72 * 2 * (int64_t)d->cin * cout_pad(d->cout); }      // (parity class, class) x 2 taps
+PackedLayout packed_layout(const s3r_conv_desc* d, const Geo& g) {
+    PackedLayout at = {0, -1, -1, -1, -1, 0};
+    int64_t end = (d->op == S3R_OP_DECONV ? 64 : ipow(d->k, g.nd)) * d->cin * cout_pad(d->cout);
+    if (wino_layer(d)) { at.wino = end; end += wino_w_elems(d); }
+    if (wino2_ax(d) >= 0) { at.wino2 = end; end += wino2_geo(d).w_elems; }
+    if (dwino_layer(d)) { at.dwino = end; end += dwino_w_elems(d); }
+    if (dwino3_layer(d)) { at.dwino3 = end; end += s3r::dwino3_w_elems(d->cin, d->cout); }
+    at.total = end; return at;
+}
 // The depth differences of the transposed Winograd form are materialised (two more tensors behind the row differences) while
 // the four tensors stay in the Infinity Cache, and formed inside the class kernel otherwise: same bits either way, so this
 // may follow the batch (s3r_conv_wino.hip).
@@ -670,7 +680,6 @@ s3r::ConvParamsH make_params_h(const s3r_conv_desc* d, const Geo& g) {
 }
 
 // (position-tile multiplier TM, split-K) of a bf16 MFMA layer
-
 int resolve_launch_h(const s3r_conv_desc* d, s3r::ConvParamsH* p, LaunchH* L) {
     const int chunks = d->cin / 32;
     if (d->ksplit < 0 || (d->ksplit > 0 && chunks % d->ksplit != 0))
@@ -717,9 +726,7 @@ s3r::ConvParams make_params(const s3r_conv_desc* d, const Geo& g) {
     if (leaky_fused(d)) { p.act = S3R_ACT_RELU; p.slope = d->act_param; }      // max(t, slope t) in the direct kernel's epilogue
     else if (p.act > S3R_ACT_SIGMOID) p.act = S3R_ACT_NONE;     // (ELU / Tanh, LeakyReLU with a slope outside [0, 1]: launch_act behind the convolution)
     p.Ntotal = p.B * p.Nd * p.Nh * p.Nw;
-    p.dS = s3r::FastDiv((unsigned)(p.Nd * p.Nh * p.Nw));
-    p.dHW = s3r::FastDiv((unsigned)(p.Nh * p.Nw));
-    p.dW = s3r::FastDiv((unsigned)p.Nw);
+    set_divs(p);
     p.ksplit = 1;
     return p;
 }
@@ -744,9 +751,7 @@ s3r::ConvParams make_params_staged(const s3r_conv_desc* d, const Geo& g) {
         p.stride = d->op == S3R_OP_DECONV ? 1 : d->stride;
     }
     p.Ntotal = p.B * p.Nd * p.Nh * p.Nw;
-    p.dS = s3r::FastDiv((unsigned)(p.Nd * p.Nh * p.Nw));
-    p.dHW = s3r::FastDiv((unsigned)(p.Nh * p.Nw));
-    p.dW = s3r::FastDiv((unsigned)p.Nw);
+    set_divs(p);
     return p;
 }
 
@@ -775,9 +780,7 @@ s3r::ConvParams make_params_tshuf(const s3r_conv_desc* d, const Geo& g) {
     p.dSC = s3r::FastDiv((unsigned)sc);
     p.dS1 = s3r::FastDiv((unsigned)s);
     p.Ntotal = p.B * p.Nd * p.Nh * p.Nw;
-    p.dS = s3r::FastDiv((unsigned)(p.Nd * p.Nh * p.Nw));
-    p.dHW = s3r::FastDiv((unsigned)(p.Nh * p.Nw));
-    p.dW = s3r::FastDiv((unsigned)p.Nw);
+    set_divs(p);
     p.ksplit = 1;
     return p;
 }
@@ -819,9 +822,7 @@ bool make_params_tclass(const s3r_conv_desc* d, const Geo& g, int rd, int rh, in
     p.y_step = s;
     p.y_org += (is3 ? (s * ad.qmin + rd - d->pad) * p.y_ds : 0) + (s * ah.qmin + rh - d->pad) * p.y_hs + (s * aw.qmin + rw - d->pad);
     p.Ntotal = p.B * p.Nd * p.Nh * p.Nw;
-    p.dS = s3r::FastDiv((unsigned)(p.Nd * p.Nh * p.Nw));
-    p.dHW = s3r::FastDiv((unsigned)(p.Nh * p.Nw));
-    p.dW = s3r::FastDiv((unsigned)p.Nw);
+    set_divs(p);
     p.ksplit = 1;
     *macs = (double)p.Ntotal * p.T * (double)sg.cin_pad * d->cout;
     *q = p;
@@ -829,7 +830,6 @@ bool make_params_tclass(const s3r_conv_desc* d, const Geo& g, int rd, int rh, in
 }
 
 // (tile cfg, gather width, split-K) of an MFMA-route layer: the caller's forced values or the heuristics
-
 int resolve_launch(const s3r_conv_desc* d, s3r::ConvParams* p, Launch* L) {
     const int chunks = d->cin / 16;
     if (d->ksplit < 0 || (d->ksplit > 0 && chunks % d->ksplit != 0))
@@ -918,6 +918,61 @@ static int handoff3d(const s3r_conv_desc& a, const s3r_conv_desc& b, bool* take)
     return lay;
 }
 
+// conv -> pointwise head fusion (fp32 path): a <=64-cout MFMA conv that does not split K, followed by the
+// 1x1 single-channel head, runs the head inside its epilogue; its own output is never materialised
+static void plan_head_fusion(Plan* pl, int n) {
+    for (int i = 0; i + 1 < n; ++i) {
+        if (pl->r[i] != R_MFMA || pl->r[i + 1] != R_HEAD || pl->d[i].cout > 64) continue;
+        if (pl->d[i + 1].cin != pl->d[i].cout || pl->d[i].out_halo != 0 || pl->d[i].act >= S3R_ACT_SIGMOID || staged_layer(&pl->d[i])) continue;
+        if (pl->d[i].op == S3R_OP_CONV && resolves_to_wino(&pl->d[i])) continue;     // (the Winograd conv kernel has no fused-head epilogue)
+        if (pl->d[i].dtype == S3R_BF16) {
+            s3r::ConvParamsH ph = make_params_h(&pl->d[i], pl->g[i]);
+            LaunchH Lh;
+            if (resolve_launch_h(&pl->d[i], &ph, &Lh) != S3R_OK || Lh.ksplit != 1) continue;
+        } else {
+            int alg, form;
+            if (resolve_algo(&pl->d[i], &alg, &form) != S3R_OK) continue;
+            if (alg == ALG_DIRECT) {                     // (a Winograd form's `tile` is a launch-form code, not a tile of the direct kernel)
+                s3r::ConvParams p = make_params(&pl->d[i], pl->g[i]);
+                Launch L;
+                if (resolve_launch(&pl->d[i], &p, &L) != S3R_OK || L.ksplit != 1) continue;
+            }
+        }
+        pl->fuse_head[i] = 1;
+    }
+}
+
+// the arena: [padded chain input] [each intermediate, or the larger form of a hand-off region] [the scratch all layers share]
+static int plan_arena(Plan* pl, int n, int user_in_halo, int need0) {
+    int64_t off = 0;
+    if (pl->pad_input && pl->d[0].in_layout != S3R_LAYOUT_PLAIN)
+        return fail(S3R_ERR_INVALID, "a transformed chain input must come with its halo (in_halo = 1)");
+    if (pl->pad_input) {
+        if (user_in_halo != 0) return fail(S3R_ERR_INVALID, "chain input halo %d is smaller than the %d its first layer needs",
+                                           user_in_halo, need0);
+        pl->pad_off = 0;
+        off = align_up(pl->g[0].x_store, 256);
+    }
+    for (int i = 0; i + 1 < n; ++i) {
+        pl->off[i] = off;
+        if (i == 0 && pl->stem_wino) off = align_up(off + pl->g[1].x_store, 256);      // layer 1's transformed planes
+        else if (!pl->fuse_head[i]) off = align_up(off + (pl->region[i] > pl->g[i].y_store ? pl->region[i] : pl->g[i].y_store), 256);   // a fused conv's output does not exist
+    }
+    for (int i = 0; i < n; ++i) {
+        // (a 3D hand-off pair is sized for its two-pass route, the larger: the route taken follows the launch forms, the size must not)
+        s3r_conv_desc t = pl->d[i];
+        if (i > 0 && pl->region[i - 1]) t.in_layout = S3R_LAYOUT_PLAIN;
+        if (pl->region[i]) t.out_layout = S3R_LAYOUT_PLAIN;
+        const int64_t sc = s3r_conv_scratch_elems(&t);
+        if (sc < 0) return (int)sc;
+        if (sc > pl->scratch_elems) pl->scratch_elems = sc;
+    }
+    pl->scratch_off = off;
+    off = align_up(off + pl->scratch_elems, 256);
+    pl->total = off;
+    return S3R_OK;
+}
+
 int plan_chain(const s3r_layer* layers, int n, Plan* pl) {
     if (!layers || n <= 0) return fail(S3R_ERR_INVALID, "empty chain");
     pl->d.resize(n); pl->r.resize(n); pl->g.resize(n); pl->off.assign(n, -1); pl->fuse_head.assign(n, 0); pl->region.assign(n, 0);
@@ -1002,54 +1057,8 @@ int plan_chain(const s3r_layer* layers, int n, Plan* pl) {
                 return fail(S3R_ERR_INVALID, "layer %d needs a halo but reshapes layer %d's output", i, i - 1);
         }
     }
-    // conv -> pointwise head fusion (fp32 path): a <=64-cout MFMA conv that does not split K, followed by the
-    // 1x1 single-channel head, runs the head inside its epilogue; its own output is never materialised
-    for (int i = 0; i + 1 < n; ++i) {
-        if (pl->r[i] != R_MFMA || pl->r[i + 1] != R_HEAD || pl->d[i].cout > 64) continue;
-        if (pl->d[i + 1].cin != pl->d[i].cout || pl->d[i].out_halo != 0 || pl->d[i].act >= S3R_ACT_SIGMOID || staged_layer(&pl->d[i])) continue;
-        if (pl->d[i].op == S3R_OP_CONV && resolves_to_wino(&pl->d[i])) continue;     // (the Winograd conv kernel has no fused-head epilogue)
-        if (pl->d[i].dtype == S3R_BF16) {
-            s3r::ConvParamsH ph = make_params_h(&pl->d[i], pl->g[i]);
-            LaunchH Lh;
-            if (resolve_launch_h(&pl->d[i], &ph, &Lh) != S3R_OK || Lh.ksplit != 1) continue;
-        } else {
-            int alg, form;
-            if (resolve_algo(&pl->d[i], &alg, &form) != S3R_OK) continue;
-            if (alg == ALG_DIRECT) {                     // (a Winograd form's `tile` is a launch-form code, not a tile of the direct kernel)
-                s3r::ConvParams p = make_params(&pl->d[i], pl->g[i]);
-                Launch L;
-                if (resolve_launch(&pl->d[i], &p, &L) != S3R_OK || L.ksplit != 1) continue;
-            }
-        }
-        pl->fuse_head[i] = 1;
-    }
-    int64_t off = 0;
-    if (pl->pad_input && pl->d[0].in_layout != S3R_LAYOUT_PLAIN)
-        return fail(S3R_ERR_INVALID, "a transformed chain input must come with its halo (in_halo = 1)");
-    if (pl->pad_input) {
-        if (user_in_halo != 0) return fail(S3R_ERR_INVALID, "chain input halo %d is smaller than the %d its first layer needs",
-                                           user_in_halo, need0);
-        pl->pad_off = 0;
-        off = align_up(pl->g[0].x_store, 256);
-    }
-    for (int i = 0; i + 1 < n; ++i) {
-        pl->off[i] = off;
-        if (i == 0 && pl->stem_wino) off = align_up(off + pl->g[1].x_store, 256);      // layer 1's transformed planes
-        else if (!pl->fuse_head[i]) off = align_up(off + (pl->region[i] > pl->g[i].y_store ? pl->region[i] : pl->g[i].y_store), 256);   // a fused conv's output does not exist
-    }
-    for (int i = 0; i < n; ++i) {
-        // (a 3D hand-off pair is sized for its two-pass route, the larger: the route taken follows the launch forms, the size must not)
-        s3r_conv_desc t = pl->d[i];
-        if (i > 0 && pl->region[i - 1]) t.in_layout = S3R_LAYOUT_PLAIN;
-        if (pl->region[i]) t.out_layout = S3R_LAYOUT_PLAIN;
-        const int64_t sc = s3r_conv_scratch_elems(&t);
-        if (sc < 0) return (int)sc;
-        if (sc > pl->scratch_elems) pl->scratch_elems = sc;
-    }
-    pl->scratch_off = off;
-    off = align_up(off + pl->scratch_elems, 256);
-    pl->total = off;
-    return S3R_OK;
+    plan_head_fusion(pl, n);
+    return plan_arena(pl, n, user_in_halo, need0);
 }
 
 }  // namespace s3rh
@@ -1085,8 +1094,7 @@ int s3r_conv_packed_elems(const s3r_conv_desc* d, int64_t* elems) {
             if (staged_layer(d)) { *elems = ipow(d->k, g.nd) * staged_geo(d).cin_pad * cout_pad(d->cout); break; }
             const int64_t taps = d->op == S3R_OP_DECONV ? 64 : ipow(d->k, g.nd);
             if (d->dtype == S3R_BF16) *elems = (taps * d->cin * cout_pad_h(d->cout) + 1) / 2;   // bf16, in float units
-            else *elems = taps * d->cin * cout_pad(d->cout) + (wino_layer(d) ? wino_w_elems(d) : 0) + (dwino_layer(d) ? dwino_w_elems(d) : 0) +
-                          (wino2_ax(d) >= 0 ? wino2_geo(d).w_elems : 0) + (dwino3_layer(d) ? s3r::dwino3_w_elems(d->cin, d->cout) : 0);
+            else *elems = packed_layout(d, g).total;
             break;
         }
     }

@@ -129,6 +129,8 @@ def _conv_cases():
         ConvCase("tclass-noTap-deconv2d-16to16-k2s3-e5", L("t", "deconv2d", 16, 16, 2, 3, 0), 5, 2, out_halo=1),
         ConvCase("tclass-deconv3d-16to16-k3s2p1op1-e5", L("t", "deconv3d", 16, 16, 3, 2, 1, True, "relu", 1, 1), 5, 2),
         ConvCase("tclass-staged-deconv3d-8to12-k4s2-e5", L("t", "deconv3d", 8, 12, 4, 2, 1), 5, 2, out_halo=1),
+        # 4^3 = 64 residue classes, more than one class table holds (kTClsMax = 27): one launch per class; output edge 13
+        ConvCase("tclass-perclass-deconv3d-16to16-k5s4-e3", L("t", "deconv3d", 16, 16, 5, 4, 0), 3, 2),
         ConvCase("tclass-inplace-h3-deconv2d-32to16-k7s2-e8", L("t", "deconv2d", 32, 16, 7, 2, 0), 8, 2, in_halo=3),
         ConvCase("tclass-inplace-h1-deconv2d-64to32-k4s2-e16", L("t", "deconv2d", 64, 32, 4, 2, 1), 16, 2, in_halo=1, out_halo=1),
         ConvCase("d2s-deconv2d-32to24-k3s3-e7", L("t", "deconv2d", 32, 24, 3, 3, 0), 7, 2, out_halo=2),
