@@ -12,11 +12,12 @@ from . import arch_spec, checkpoint, collate, data, evaluate, exr
 from .graph import GraphedForward, PrefetchingLoader
 from ._lib import ALGO_AUTO, ALGO_DIRECT, ALGO_WINOGRAD, S3RError, LIB_PATH, load as load_library, profile_enable, profile_read, profile_reset, profile_detail
 from .init import seed_module, seeded_state_dict, synthetic_pairs
-from .modules import (ChamferDistance, CostVolume, Decoder, Encoder, PointHead, Stereo2Point, Stereo2Voxel,
-                      VolumeEncoder, chamfer_distance, chamfer_distance_backward, differentiable_chamfer_distance, linear, linear_backward, differentiable_linear, VoxelBCELoss, voxel_bce, voxel_bce_backward, differentiable_voxel_bce, head, head_backward, differentiable_head, conv_forward, conv_backward, differentiable_conv, stem_backward, batchnorm_train_forward, batchnorm_train_backward, differentiable_batchnorm, cost_volume_backward, differentiable_cost_volume, cost_volume, debug_overrides, decoder, disparity_epe, disparity_wta,
-                      disparity_soft, disparity_metrics, DISPARITY_TEMPERATURE, encoder, voxel_iou,
-                      disparity_soft_backward, differentiable_disparity_soft, DisparityLoss, disparity_loss, disparity_loss_backward,
-                      differentiable_disparity_loss)
+from .modules import (CostVolume, Decoder, Encoder, PointHead, Stereo2Point, Stereo2Voxel, VolumeEncoder, cost_volume, debug_overrides,
+                      decoder, DISPARITY_TEMPERATURE, encoder)
+from .ops import (ChamferDistance, chamfer_distance, chamfer_distance_backward, differentiable_chamfer_distance, linear, linear_backward, differentiable_linear, VoxelBCELoss, voxel_bce, voxel_bce_backward, differentiable_voxel_bce, head, head_backward, differentiable_head, conv_forward, conv_backward, differentiable_conv, stem_backward, batchnorm_train_forward, batchnorm_train_backward, differentiable_batchnorm, cost_volume_backward, differentiable_cost_volume, disparity_epe, disparity_wta,
+                  disparity_soft, disparity_metrics, voxel_iou,
+                  disparity_soft_backward, differentiable_disparity_soft, DisparityLoss, disparity_loss, disparity_loss_backward,
+                  differentiable_disparity_loss)
 from .optim import SGD, Adam, AdamW
 
 __all__ = [

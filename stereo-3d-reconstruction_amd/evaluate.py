@@ -14,7 +14,8 @@ import torch
 
 from . import arch_spec as spec
 from . import collate
-from .modules import READOUTS, chamfer_distance, disparity_metrics, voxel_iou
+from .modules import READOUTS
+from .ops import chamfer_distance, disparity_metrics, voxel_iou
 
 THRESHOLDS = (0.2, 0.3, 0.4, 0.5)
 

@@ -123,10 +123,10 @@ GPU_IDS = [c.id for c in SINGLE_CASES] + [c.id for c in CHAIN_CASES]
 assert len(set(GPU_IDS)) == len(GPU_IDS)
 
 
-def _read_records(lib):
-    buf = (P.ProfRecord * 256)()
-    n = lib.s3r_profile_read(buf, 256)
-    assert 0 <= n < 256, n
+def _read_records(lib, cap=256):
+    buf = (P.ProfRecord * cap)()
+    n = lib.s3r_profile_read(buf, cap)
+    assert 0 <= n < cap, n
     return [dict([(k, int(getattr(r, k))) for k in REC_INTS] + [(k, float(getattr(r, k))) for k in REC_DOUBLES]) for r in buf[:n]]
 
 

@@ -592,7 +592,8 @@ def test_release_path_reads_no_kernel_policy_from_the_environment(s3r, monkeypat
     """descriptor fields come from the model, its tuning tables or an explicit s3r.debug_overrides(...)
     context — never from os.environ (r05 read S3R_TILE_ / S3R_KSPLIT_ / S3R_ALGO_<layer> on every forward)."""
     import re
-    src = open(os.path.join(ROOT, "stereo-3d-reconstruction_amd", "modules.py")).read()
+    # every file of the package that builds a descriptor, as one text (modules.py first: the one use is in it)
+    src = "\n".join(open(os.path.join(ROOT, "stereo-3d-reconstruction_amd", f)).read() for f in ("modules.py", "ops.py", "_tensors.py"))
     uses = [l.strip() for l in src.split("\n") if "os.environ" in l and not l.strip().startswith("#")]
     assert len(uses) == 1 and "S3R_BF16_MFMA" in uses[0] and "_cache_key" in src[:src.index(uses[0])].rsplit("def ", 1)[1]
     for name in ("S3R_TILE_v2", "S3R_KSPLIT_v2", "S3R_ALGO_v2"):
