@@ -48,6 +48,8 @@
  *   s3r_optim_step (+ s3r_optim_state_init, torch.optim.SGD / Adam / AdamW's step and torch.nn.utils.clip_grad_norm_: the parameter update
  *   s3r_optim_set_lr, its scratch query)    of `python3 runner.py` (training), with a defined rounding order and its step count, powers
  *                                           and learning rate on the device                (README.md:36,77)
+ *   s3r_augment_pair (+ its scratch query)  the input augmentation of `python3 runner.py` (training) on 8-bit stereo renders, the
+ *                                           disparity maps shifted along; the transform set is INVENTED by this build (README.md:36,77)
  *
  * Conventions
  *   - every tensor is fp32, contiguous, NCHW / NCDHW, resident in device memory owned by the caller;
@@ -90,7 +92,8 @@ extern "C" {
  * query) likewise; s3r_cost_volume_backward likewise; s3r_batchnorm_train_forward and s3r_batchnorm_train_backward (+ their scratch queries)
  * likewise; s3r_stem_backward (+ its scratch query) likewise; s3r_disparity_soft_backward, s3r_disparity_loss_forward and
  * s3r_disparity_loss_backward likewise; s3r_optim_step, s3r_optim_state_init, s3r_optim_set_lr and s3r_optim_scratch_elems (with their two
- * structs) likewise: new entry points only, the version stays 8. */
+ * structs) likewise; s3r_augment_pair and s3r_augment_scratch_elems (with their struct) likewise: new entry points only, the version
+ * stays 8. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -891,6 +894,79 @@ int s3r_optim_state_init(float* state, float lr, void* hip_stream);
 int s3r_optim_set_lr(float* state, float lr, void* hip_stream);
 int s3r_optim_step(const s3r_optim_desc* d, const s3r_optim_tensor* t, int n_tensors, float* state, float* scratch,
                    int64_t scratch_elems, void* hip_stream);
+
+/* Training-time augmentation of a stereo batch: 8-bit renders in, fp32 network inputs in [0, 1] out, with the ground-truth disparity maps
+ * shifted by the same call.  Deterministic, atomics-free, nothing drawn or read on the host: a sample's result is a function of (seed,
+ * sample_ids[b]) and its own pixels only — not of its batch, its position in the batch, an address or the launch shape — and a captured
+ * call replays with fresh augmentation from the ids in the device buffer.  The transform set and its constants are INVENTED by this build
+ * (the reference's own transforms are on unmounted branches), to be overwritten from the reference the day it is mounted.
+ *
+ * Tensors.  left, right (B, channels, H, W) uint8 codes at any byte alignment; channels = 3 (RGB) or 4 (RGBA, alpha composited in the
+ * kernel over the drawn background).  sample_ids (B) int64 ON THE DEVICE.  out_left, out_right (B, 3, H, W) fp32, 4-byte aligned.
+ * disp_left, disp_right, out_disp_left, out_disp_right: all NULL or all given, (B, H, W) fp32 maps in render pixels.  H and W are general.
+ *
+ * Random numbers.  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85), key = (seed low, seed
+ * high), counter = (id low, id high, purpose, index) with id = sample_ids[b]; w0..w3 are its four output words.
+ * u(w) = (float)(w >> 8) * 2^-24 (exact).  range(u, lo, hi):  t = hi - lo;  t = u * t;  lo + t.
+ * Every draw is made whether or not its op is enabled: switching one op on never changes another op's draw.
+ *   purpose 0, index 0:   dy = w0 % (2 max_shift + 1) - max_shift;  dx likewise from w1;  perm = w2 % 6, an index into the lexicographic
+ *                         permutations of (0, 1, 2).  The modulo's bias (below 2^-18 for max_shift <= 4096) is accepted.
+ *   purpose 0, index 1:   brightness = range(u(w0), ...), contrast = range(u(w1), ...), saturation = range(u(w2), ...)
+ *   purpose 0, index 2:   bg[c] = bg_lo + w_c % (bg_hi - bg_lo + 1), c = 0..2
+ *   purpose 1 + 3 side + c (side 0 left, 1 right; c the source channel), index y W + x:  the four noise words of that output pixel
+ * All per-pair parameters are shared by the two views (the epipolar geometry and the disparity survive); only the noise is per view.
+ *
+ * Arithmetic.  Everything is fp32, every operation is rounded on its own (nothing contracted into a fused multiply-add), division is
+ * the correctly rounded IEEE one; clamp(v) = fminf(fmaxf(v, 0), 1).  Per output pixel (y, x) of one view, over the three source channels c:
+ *   1. source pixel:   sy = y - dy, sx = x - dx.  Outside the image: code = bg[c].  Inside, 3 channels: code = src[c].  Inside, 4
+ *                      channels, with a = src[3]: code = (src[c] * a + bg[c] * (255 - a) + 127) / 255 in unsigned integers
+ *   2. scale:          v = (float)code / 255.f
+ *   3. brightness      (unless brightness_lo == brightness_hi == 1):  v = brightness * v;  v = clamp(v)
+ *   4. contrast        (unless contrast_lo == contrast_hi == 1), m the pair's mean luma (below):
+ *                      a = contrast * v;  t = 1.f - contrast;  b = t * m;  v = a + b;  v = clamp(v)
+ *   5. saturation      (unless saturation_lo == saturation_hi == 1), l = (0.299f * v0 + 0.587f * v1) + 0.114f * v2 of the pixel after step 4:
+ *                      a = saturation * v;  t = 1.f - saturation;  b = t * l;  v = a + b;  v = clamp(v)
+ *   6. noise           (unless noise_sigma == 0):  s = u(w0) + u(w1);  s = s + u(w2);  s = s + u(w3);  s = s - 2.f;  s = s * 1.7320508f;
+ *                      s = noise_sigma * s;  v = v + s;  v = clamp(v)      (an Irwin-Hall sum of unit variance: no logf, no cosf)
+ *   7. store:          out[c'] = v[perm[c']] with S3R_AUG_PERMUTE_RGB, out[c] = v[c] without it
+ * Disparity: out_disp(y, x) = disp(sy, sx) copied bit for bit inside the image (NaNs and their payloads included), +inf — the loaders'
+ * invalid marker — outside it.
+ *
+ * The mean luma m is ONE value per pair: both views are blended towards the same grey.  The lumas l (step 5's formula) of the left and
+ * of the right view after step 3 form two rows of S = H W positions, summed in the order of s3r_head_backward's sums with B = 2 rows:
+ * chunks of 512 consecutive positions (the last may be short: missing positions count as +0.0); within a chunk lane L (0..63) owns the
+ * eight positions 256 j + 4 L + i (j = 0, 1; i = 0..3) and adds its lumas in ascending position to a partial that starts as +0.0; the 64
+ * partials are combined by the halving tree v[L] = v[L] + v[L + o] for L < o, o = 32, 16, 8, 4, 2, 1; each view's chunk sums are added in
+ * ascending chunk order into a partial that starts as its chunk 0's sum; total = left + right;  m = total / (float)(2 S).
+ *
+ * scratch: s3r_augment_scratch_elems(d, batch, height, width) floats = 2 B ceil(S / 512) + B with contrast (the chunk sums and the
+ * means), 0 without (it may be NULL); its contents on entry do not matter.  The query returns S3R_ERR_INVALID for what the call refuses.
+ * Refused with S3R_ERR_INVALID and a message, host-side, before anything is enqueued: a NULL d, left, right, sample_ids, out_left or
+ * out_right; disparity pointers partly given; channels not 3 or 4; batch, height or width <= 0, H W >= 2^31 or a tensor of 2^31
+ * elements or more; max_shift < 0 or > 4096; an unknown flag bit; bg_lo or bg_hi outside 0..255 or bg_lo > bg_hi; a range with lo > hi,
+ * negative or non-finite; noise_sigma negative or non-finite; with contrast, scratch NULL or scratch_elems below the query; outputs
+ * (and the scratch) that overlap an input or each other.
+ * Launches: without contrast ONE (apply); with contrast three — the chunk sums, one wave per pair writing m, then apply, which
+ * recomputes steps 1-3 and stores no intermediate image.  Every node is a kernel (no memset, no copy).
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new renders and ids in the same buffers).
+ * Profiler: no record (the call is meant to be captured, and the event profiler must be off while capturing). */
+#define S3R_AUG_PERMUTE_RGB 1
+#define S3R_AUG_MAX_SHIFT 4096
+typedef struct s3r_augment_desc {
+    uint64_t seed;
+    int32_t  channels;            /* 3 = RGB codes, 4 = RGBA codes (alpha composited in the kernel) */
+    int32_t  max_shift;           /* 0 = off */
+    int32_t  flags;               /* S3R_AUG_PERMUTE_RGB = 1 */
+    int32_t  bg_lo, bg_hi;        /* background codes, 0 <= lo <= hi <= 255 */
+    float    brightness_lo, brightness_hi, contrast_lo, contrast_hi, saturation_lo, saturation_hi;
+    float    noise_sigma;         /* in [0,1] units; 0 = off */
+} s3r_augment_desc;
+int64_t s3r_augment_scratch_elems(const s3r_augment_desc* d, int batch, int height, int width);
+int s3r_augment_pair(const s3r_augment_desc* d, const uint8_t* left, const uint8_t* right, const int64_t* sample_ids,
+                     const float* disp_left, const float* disp_right, float* out_left, float* out_right,
+                     float* out_disp_left, float* out_disp_right, int batch, int height, int width,
+                     float* scratch, int64_t scratch_elems, void* hip_stream);
 
 /* Kernel-level profiler: when enabled, every kernel the library launches is bracketed by HIP events
  * on the launch stream.  s3r_profile_read synchronises those events and returns, per launch, the

@@ -5,8 +5,11 @@
     python3 runner.py --test --gpus 8 ...             (starts its own 8 ranks, one process per GPU, as a child)
     python -m torch.distributed.run --nproc-per-node 8 runner.py --test ...   (or under an external launcher)
 
-Only `--test` exists here: the forward/inference path is what this build implements (training is out of
-scope) and `python3 runner.py` without --test says so.  Without --weights the model
+    python3 runner.py --train --out runs/a [--dataset-root ... | --data x.npz] [--resume runs/a/last.pth]
+
+`--test` evaluates and `--train` trains (s3r.train.fit: one GPU, fp32; deterministic on-device augmentation, the HIP losses and
+optimizer step, validation through the --test path, checkpoints that carry the optimizer; one JSON line per epoch).  `python3
+runner.py` with neither says so and exits non-zero.  Without --weights the model
 is seeded random-init (BASELINE.json configs[0]); with it the checkpoint goes through
 s3r.checkpoint.load_checkpoint (container unwrapping + keymap.json).  There is no dataset in this
 environment (README.md:29 is a download link), so the eval list is synthetic unless --data names an
@@ -30,7 +33,19 @@ if ROOT not in sys.path:
 
 def main():
     ap = argparse.ArgumentParser(description="Stereo2Voxel / Stereo2Point evaluation on MI355X")
-    ap.add_argument("--test", action="store_true", help="evaluate (the only mode this build implements)")
+    ap.add_argument("--test", action="store_true", help="evaluate")
+    ap.add_argument("--train", action="store_true", help="train (one GPU, fp32): prints one JSON line per epoch")
+    ap.add_argument("--epochs", type=int, default=1, help="--train: epochs to run in total (a resumed run counts from its checkpoint)")
+    ap.add_argument("--lr", type=float, default=1e-3, help="--train: learning rate")
+    ap.add_argument("--milestones", default="", help="--train: comma-separated epochs at which the learning rate is multiplied by --gamma")
+    ap.add_argument("--gamma", type=float, default=0.1, help="--train: the multi-step schedule's factor")
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "adamw", "sgd"], help="--train: s3r.Adam, s3r.AdamW or s3r.SGD (momentum 0.9)")
+    ap.add_argument("--augment", default="default", choices=["none", "default"],
+                    help="--train: none (the renders as they are) or default (s3r.AugmentConfig.default(): shift, channel permutation, "
+                         "brightness / contrast / saturation jitter, noise — a transform set this build invented)")
+    ap.add_argument("--out", default=None, help="--train: directory for last.pth / best.pth")
+    ap.add_argument("--resume", default=None, help="--train: a checkpoint written by an earlier --train run to continue from")
+    ap.add_argument("--val-samples", type=int, default=None, help="--train: length of the validation list (default: a tenth, at least 2)")
     ap.add_argument("--weights", default=None, help="checkpoint (.pth) to load")
     ap.add_argument("--keymap", default=None, help="JSON: reference state_dict key -> this build's key")
     ap.add_argument("--suggest-keymap", action="store_true",
@@ -96,8 +111,16 @@ def main():
         print(json.dumps(s3r.checkpoint.suggest_keymap(torch.load(args.weights, map_location="cpu", weights_only=True), m),
                          indent=1))
         return
+    if args.train:
+        if args.test:
+            sys.exit("runner.py: --train and --test are two runs: name one")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.force_dist:
+            sys.exit("runner.py --train runs on one GPU: there is no gradient all-reduce (--gpus > 1 is for --test)")
+        if args.precision != "fp32":
+            sys.exit("runner.py --train trains fp32 models only: there is no bf16 backward")
+        return train_main(args)
     if not args.test:
-        sys.exit("runner.py: only --test is implemented (forward/inference path; training is out of scope)")
+        sys.exit("runner.py: only --test is implemented for evaluation, and --train for training: name one of them")
 
     import numpy as np
     import torch
@@ -252,6 +275,59 @@ def main():
         print(json.dumps(out))
     if dist_on:
         dist.destroy_process_group()
+
+
+def train_main(args):
+    import numpy as np
+    import torch
+    import s3r
+    from s3r import train as T
+
+    if not torch.cuda.is_available():
+        sys.exit("runner.py --train needs an MI355X: this path has no CPU fallback")
+    dev = torch.device("cuda", 0)
+    model = s3r.Stereo2Voxel("fp32") if args.variant == "voxel" else s3r.Stereo2Point("fp32")
+    if args.weights:
+        s3r.checkpoint.load_checkpoint(model, args.weights, json.load(open(args.keymap)) if args.keymap else None)
+    else:
+        s3r.seed_module(model, args.seed)
+    model.to(dev)
+
+    if args.dataset_root:
+        if args.variant == "point":
+            sys.exit("runner.py --variant point reads an .npz (left, right, points) or synthetic data, not a dataset tree")
+        full = s3r.data.StereoShapeNet(args.dataset_root, with_disparity=args.disparity, render_channels=4 if args.augment == "default" else 3)
+        n = len(full)
+    else:
+        if args.data:
+            z = np.load(args.data)
+            fields = [torch.from_numpy(z["left"]), torch.from_numpy(z["right"]),
+                      torch.from_numpy(z["points" if args.variant == "point" else "volume"]).float()]
+            if fields[0].dtype != torch.uint8:
+                sys.exit("runner.py --train reads 8-bit renders: the .npz arrays left / right must be uint8")
+            if "disp_left" in z.files and "disp_right" in z.files and tuple(z["disp_left"].shape[1:]) == tuple(fields[0].shape[2:]):
+                fields += [torch.from_numpy(z["disp_left"]).float(), torch.from_numpy(z["disp_right"]).float()]
+        else:
+            left, right, gt = s3r.evaluate.synthetic_eval_set(args.samples, args.seed, "uint8")
+            if args.variant == "point":
+                gt = torch.rand(args.samples, 2048, 3, generator=torch.Generator().manual_seed(args.seed)) - 0.5
+            fields = [left, right, gt]
+        full = torch.utils.data.TensorDataset(*fields)
+        n = fields[0].shape[0]
+    n_val = min(n - 1, args.val_samples if args.val_samples is not None else max(2, n // 10))
+    if n_val > 0:                                        # the LAST n_val items of the list validate, the rest train
+        train_set = torch.utils.data.Subset(full, range(n - n_val))
+        val_set = torch.utils.data.Subset(full, range(n - n_val, n))
+    else:
+        train_set, val_set = full, None
+    with_disp = len(full[0]) >= 5
+    cfg = T.TrainConfig(variant=args.variant, epochs=args.epochs, batch=args.batch, lr=args.lr, optimizer=args.optimizer,
+                        milestones=tuple(int(m) for m in args.milestones.split(",") if m.strip()), gamma=args.gamma,
+                        augment=s3r.AugmentConfig.default(args.seed) if args.augment == "default" else s3r.AugmentConfig.identity(args.seed),
+                        disparity_weight=1.0 if with_disp else 0.0, out_dir=args.out, resume=args.resume, seed=args.seed, workers=args.workers)
+    res = T.fit(model, train_set, val_set, cfg, log=T.json_line)
+    print(json.dumps({"done": True, "epochs": res["epoch"], "steps": res["step"], "best": res["best"], "checkpoint": res["checkpoint"],
+                      "train_samples": len(train_set), "val_samples": 0 if val_set is None else len(val_set)}))
 
 
 if __name__ == "__main__":

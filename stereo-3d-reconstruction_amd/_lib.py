@@ -25,6 +25,7 @@ ALGO = {None: 0, "auto": 0, "direct": 1, "winograd": 2, False: 1, True: 2}
 OPT_SGD, OPT_ADAM = 0, 1                            # s3r_optim_desc.kind
 OPT_DECOUPLED_DECAY, OPT_NESTEROV, OPT_CLIP, OPT_SKIP_NONFINITE = 1, 2, 4, 8      # s3r_optim_desc.flags
 OPTIM_TENSORS_PER_LAUNCH, OPTIM_MAX_TENSORS, OPTIM_STATE_DWORDS = 64, 4096, 8
+AUG_PERMUTE_RGB, AUG_MAX_SHIFT = 1, 4096            # s3r_augment_desc.flags; the largest max_shift
 FORM_CUT, FORM_ONE_LAUNCH, FORM_RING = 1, 2, 4      # s3r_prof_record.launch_form (include/s3r.h)
 RAN = {0: "direct", 1: "winograd-serial", 2: "winograd-class-parallel", 3: "winograd-dual", 4: "winograd-2axis", 5: "winograd-3axis", 6: "winograd-3axis-class-parallel"}
 
@@ -53,6 +54,12 @@ class OptimTensor(C.Structure):
 class OptimDesc(C.Structure):
     _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
                 ("weight_decay", C.c_float), ("max_norm", C.c_float)]
+
+
+class AugmentDesc(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("channels", C.c_int32), ("max_shift", C.c_int32), ("flags", C.c_int32), ("bg_lo", C.c_int32),
+                ("bg_hi", C.c_int32), ("brightness_lo", C.c_float), ("brightness_hi", C.c_float), ("contrast_lo", C.c_float),
+                ("contrast_hi", C.c_float), ("saturation_lo", C.c_float), ("saturation_hi", C.c_float), ("noise_sigma", C.c_float)]
 
 
 class S3RError(RuntimeError):
@@ -138,6 +145,9 @@ SIGNATURES = {
     "s3r_optim_state_init": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
     "s3r_optim_set_lr": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
     "s3r_optim_step": (C.c_int, [C.POINTER(OptimDesc), C.POINTER(OptimTensor), C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "s3r_augment_scratch_elems": (C.c_int64, [C.POINTER(AugmentDesc), C.c_int, C.c_int, C.c_int]),
+    "s3r_augment_pair": (C.c_int, [C.POINTER(AugmentDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "s3r_profile_enable": (C.c_int, [C.c_int]),
     "s3r_profile_reset": (C.c_int, []),
     "s3r_profile_detail": (C.c_int, [C.c_int]),

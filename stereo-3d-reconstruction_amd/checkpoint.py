@@ -118,3 +118,41 @@ def load_checkpoint(model: torch.nn.Module, path: str, keymap: Optional[Dict[str
         raise RuntimeError(f"state_dict mismatch: missing {missing[:8]}{'...' if len(missing) > 8 else ''}, "
                            f"unexpected {unexpected[:8]}; extend {KEYMAP_PATH}")
     return missing, unexpected
+
+
+# ---------------------------------------------------------------- training checkpoints (train.fit)
+TRAINING_KEYS = ("model", "optimizer", "epoch", "step", "best", "config")
+
+
+def _to_cpu(obj):
+    if isinstance(obj, torch.Tensor):
+        return obj.detach().cpu().clone()
+    if isinstance(obj, dict):
+        return {k: _to_cpu(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_cpu(v) for v in obj)
+    return obj
+
+
+def save_checkpoint(path: str, model: torch.nn.Module, optimizer, epoch: int, step: int, best, config: dict) -> str:
+    """A training checkpoint `{"model", "optimizer", "epoch", "step", "best", "config"}` with every tensor on the CPU: the model's
+    state_dict, the optimizer's (the s3r optimizers carry their device state — step count, running powers, learning rate — in it), the
+    epoch and global step the NEXT step belongs to, the best validation score so far and the run's configuration as plain Python
+    values.  `unwrap` finds "model", so `load_checkpoint` (and `runner.py --test --weights`) reads the file as it is.  Written to a
+    temporary name and renamed: an interrupted save leaves the previous file."""
+    obj = {"model": _to_cpu(model.state_dict()), "optimizer": _to_cpu(optimizer.state_dict()), "epoch": int(epoch), "step": int(step),
+           "best": best, "config": config}
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    tmp = path + ".tmp"
+    torch.save(obj, tmp)
+    os.replace(tmp, path)
+    return path
+
+
+def load_training_checkpoint(path: str) -> dict:
+    """The dict `save_checkpoint` wrote (tensors on the CPU); raises when a key is missing."""
+    obj = torch.load(path, map_location="cpu", weights_only=True)
+    missing = [k for k in TRAINING_KEYS if not isinstance(obj, dict) or k not in obj]
+    if missing:
+        raise RuntimeError(f"{path} is not a training checkpoint: no {missing}")
+    return obj

@@ -1529,4 +1529,81 @@ int s3r_optim_step(const s3r_optim_desc* d, const s3r_optim_tensor* t, int n_ten
     return S3R_OK;
 }
 
+// ---------------------------------------------------------------- stereo augmentation (s3r_augment.hip)
+namespace {
+
+bool augment_bad_range(float lo, float hi) { return !std::isfinite(lo) || !std::isfinite(hi) || lo < 0.f || lo > hi; }
+
+// the descriptor's and the shape's own checks, shared by the query and the call
+int augment_shape(const s3r_augment_desc* d, int batch, int height, int width) {
+    if (!d) return fail(S3R_ERR_INVALID, "augment: null descriptor");
+    if (d->channels != 3 && d->channels != 4) return fail(S3R_ERR_INVALID, "augment: channels = %d must be 3 (RGB) or 4 (RGBA)", d->channels);
+    if (batch <= 0 || height <= 0 || width <= 0)
+        return fail(S3R_ERR_INVALID, "augment: batch = %d, height = %d, width = %d must be positive", batch, height, width);
+    const int64_t S = (int64_t)height * width;
+    if (S >= kMaxElems) return fail(S3R_ERR_INVALID, "augment: height * width = %lld must be below 2^31", (long long)S);
+    if ((int64_t)batch > (kMaxElems - 1) / (d->channels * S))
+        return fail(S3R_ERR_INVALID, "augment: a tensor of the call has 2^31 elements or more: split the batch");
+    if (d->max_shift < 0 || d->max_shift > S3R_AUG_MAX_SHIFT)
+        return fail(S3R_ERR_INVALID, "augment: max_shift = %d must be in [0, %d]", d->max_shift, S3R_AUG_MAX_SHIFT);
+    if (d->flags & ~S3R_AUG_PERMUTE_RGB) return fail(S3R_ERR_INVALID, "augment: unknown flag bits 0x%x", d->flags & ~S3R_AUG_PERMUTE_RGB);
+    if (d->bg_lo < 0 || d->bg_hi > 255 || d->bg_lo > d->bg_hi)
+        return fail(S3R_ERR_INVALID, "augment: background codes [%d, %d] must satisfy 0 <= lo <= hi <= 255", d->bg_lo, d->bg_hi);
+    if (augment_bad_range(d->brightness_lo, d->brightness_hi)) return fail(S3R_ERR_INVALID, "augment: the brightness range must be finite with 0 <= lo <= hi");
+    if (augment_bad_range(d->contrast_lo, d->contrast_hi)) return fail(S3R_ERR_INVALID, "augment: the contrast range must be finite with 0 <= lo <= hi");
+    if (augment_bad_range(d->saturation_lo, d->saturation_hi)) return fail(S3R_ERR_INVALID, "augment: the saturation range must be finite with 0 <= lo <= hi");
+    if (!std::isfinite(d->noise_sigma) || d->noise_sigma < 0.f) return fail(S3R_ERR_INVALID, "augment: noise_sigma must be finite and >= 0");
+    return S3R_OK;
+}
+
+int64_t augment_need(const s3r_augment_desc* d, int batch, int height, int width) {
+    return s3r::augment_scratch(d, batch, (int64_t)height * width);
+}
+
+struct AugSpan { const void* p; int64_t bytes; const char* name; };
+bool augment_overlap(const AugSpan& a, const AugSpan& b) {
+    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
+    return a.p && b.p && x < y + (uintptr_t)b.bytes && y < x + (uintptr_t)a.bytes;
+}
+
+}  // namespace
+
+int64_t s3r_augment_scratch_elems(const s3r_augment_desc* d, int batch, int height, int width) {
+    int rc = augment_shape(d, batch, height, width);
+    if (rc) return rc;
+    return augment_need(d, batch, height, width);
+}
+
+int s3r_augment_pair(const s3r_augment_desc* d, const uint8_t* left, const uint8_t* right, const int64_t* sample_ids,
+                     const float* disp_left, const float* disp_right, float* out_left, float* out_right,
+                     float* out_disp_left, float* out_disp_right, int batch, int height, int width,
+                     float* scratch, int64_t scratch_elems, void* hip_stream) {
+    int rc = augment_shape(d, batch, height, width);
+    if (rc) return rc;
+    if (!left || !right || !sample_ids) return fail(S3R_ERR_INVALID, "augment: null left, right or sample_ids");
+    if (!out_left || !out_right) return fail(S3R_ERR_INVALID, "augment: null out_left or out_right");
+    const int given = (disp_left != nullptr) + (disp_right != nullptr) + (out_disp_left != nullptr) + (out_disp_right != nullptr);
+    if (given != 0 && given != 4)
+        return fail(S3R_ERR_INVALID, "augment: disp_left, disp_right, out_disp_left and out_disp_right must be all NULL or all given");
+    const int64_t need = augment_need(d, batch, height, width);
+    if (need > 0 && (!scratch || scratch_elems < need))
+        return fail(S3R_ERR_INVALID, "augment: contrast needs %lld floats of scratch (s3r_augment_scratch_elems), got %lld",
+                    (long long)need, scratch ? (long long)scratch_elems : 0ll);
+    const int64_t S = (int64_t)height * width, px = (int64_t)batch * S;
+    const AugSpan outs[5] = {{out_left, 12 * px, "out_left"}, {out_right, 12 * px, "out_right"}, {out_disp_left, 4 * px, "out_disp_left"},
+                             {out_disp_right, 4 * px, "out_disp_right"}, {need > 0 ? scratch : nullptr, 4 * need, "scratch"}};
+    const AugSpan ins[5] = {{left, d->channels * px, "left"}, {right, d->channels * px, "right"}, {sample_ids, 8 * (int64_t)batch, "sample_ids"},
+                            {disp_left, 4 * px, "disp_left"}, {disp_right, 4 * px, "disp_right"}};
+    for (int i = 0; i < 5; ++i) {
+        for (int j = i + 1; j < 5; ++j)
+            if (augment_overlap(outs[i], outs[j])) return fail(S3R_ERR_INVALID, "augment: %s and %s overlap", outs[i].name, outs[j].name);
+        for (int j = 0; j < 5; ++j)
+            if (augment_overlap(outs[i], ins[j])) return fail(S3R_ERR_INVALID, "augment: %s overlaps the input %s", outs[i].name, ins[j].name);
+    }
+    hipError_t e = s3r::launch_augment_pair(d, left, right, sample_ids, disp_left, disp_right, out_left, out_right, out_disp_left,
+                                            out_disp_right, batch, height, width, scratch, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "augment launch");
+    return S3R_OK;
+}
+
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <atomic>
 
 struct s3r_optim_tensor;      // include/s3r.h
+struct s3r_augment_desc;
 
 namespace s3r {
 
@@ -393,6 +394,13 @@ hipError_t launch_optim_state_init(float* state, float lr, hipStream_t s);
 hipError_t launch_optim_set_lr(float* state, float lr, hipStream_t s);
 hipError_t launch_optim_step(int kind, int flags, float beta1, float beta2, float eps, float wd, float max_norm,
                              const ::s3r_optim_tensor* t, int n_tensors, float* state, float* scratch, hipStream_t s);
+
+// s3r_augment.hip: the stereo augmentation (include/s3r.h, s3r_augment_pair): [chunk sums of the luma + one wave per pair for the
+// mean, only with contrast] + one apply launch; augment_scratch is the floats it needs for S = H W positions (0 without contrast)
+long long augment_scratch(const ::s3r_augment_desc* d, int B, long long S);
+hipError_t launch_augment_pair(const ::s3r_augment_desc* d, const uint8_t* left, const uint8_t* right, const int64_t* ids,
+                               const float* disp_l, const float* disp_r, float* out_l, float* out_r, float* out_dl, float* out_dr, int B,
+                               int H, int W, float* scratch, hipStream_t s);
 
 #if defined(__HIPCC__)
 // Winograd F(4, 3) input transform along one axis (s3r_conv_wino.hip): the six class values of six consecutive padded rows.

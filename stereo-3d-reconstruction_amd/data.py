@@ -55,8 +55,9 @@ def renders_to_float(u8) :
     return u8.astype(np.float32) / np.float32(255.0)
 
 
-def _load_png(path: str) -> np.ndarray:
-    """One render as (3,224,224) uint8, composited over white."""
+def _load_png(path: str, channels: int = 3) -> np.ndarray:
+    """One render as (3,224,224) uint8, composited over white; channels=4: the resized RGBA codes (4,224,224), NOT composited (the
+    training augmentation composites them on the device over a background it draws)."""
     try:
         from PIL import Image
     except ImportError as e:                              # pragma: no cover
@@ -66,6 +67,8 @@ def _load_png(path: str) -> np.ndarray:
         if im.size != (IMG, IMG):
             im = im.resize((IMG, IMG), Image.BILINEAR)
         rgba = np.asarray(im, dtype=np.uint8)
+    if channels == 4:
+        return rgba.transpose(2, 0, 1).copy()
     return composite_over_white_u8(rgba).transpose(2, 0, 1).copy()          # white background, CHW
 
 
@@ -106,13 +109,19 @@ class StereoShapeNet(torch.utils.data.Dataset):
     """One item per (taxonomy, model, view): left, right (3,224,224) uint8 (render_dtype="uint8", default: the modules
     take them as they are) or float32 in [0,1] (render_dtype="float32": uint8 / 255), volume (32,32,32) {0,1};
     with_disparity=True appends the left / right ground-truth disparity maps (224,224) float32 (render pixels; the
-    files' own invalid markers — inf / negative — are kept) and lists only the views that have both EXR files."""
+    files' own invalid markers — inf / negative — are kept) and lists only the views that have both EXR files.
+    render_channels=4 yields the renders as (4,224,224) uint8 RGBA codes, resized but NOT composited: `augment.StereoAugment`
+    composites them on the device; the default 3 is unchanged."""
 
     def __init__(self, root: str, taxonomies: Optional[Sequence[str]] = None, views: Optional[Sequence[int]] = None,
-                 with_disparity: bool = False, render_dtype: str = "uint8"):
+                 with_disparity: bool = False, render_dtype: str = "uint8", render_channels: int = 3):
         if render_dtype not in ("uint8", "float32"):
             raise ValueError("render_dtype must be 'uint8' or 'float32'")
-        self.with_disparity, self.render_dtype = with_disparity, render_dtype
+        if render_channels not in (3, 4):
+            raise ValueError("render_channels must be 3 (composited over white) or 4 (RGBA codes, not composited)")
+        if render_channels == 4 and render_dtype != "uint8":
+            raise ValueError("render_channels=4 yields 8-bit RGBA codes: render_dtype must be 'uint8'")
+        self.with_disparity, self.render_dtype, self.render_channels = with_disparity, render_dtype, render_channels
         rdir = os.path.join(root, RENDER_DIR)
         if not os.path.isdir(rdir):
             raise FileNotFoundError(f"{rdir} not found (expected the layout of README.md:73-77 under {root})")
@@ -144,8 +153,8 @@ class StereoShapeNet(torch.utils.data.Dataset):
     def __getitem__(self, i):
         tax, model, view = self.items[i]
         mdir = os.path.join(self.root, RENDER_DIR, tax, model)
-        left = _load_png(os.path.join(mdir, "render_%02d_l.png" % view))
-        right = _load_png(os.path.join(mdir, "render_%02d_r.png" % view))
+        left = _load_png(os.path.join(mdir, "render_%02d_l.png" % view), self.render_channels)
+        right = _load_png(os.path.join(mdir, "render_%02d_r.png" % view), self.render_channels)
         if self.render_dtype == "float32":
             left, right = renders_to_float(left), renders_to_float(right)
         vol = _load_volume(os.path.join(self.root, VOLUME_DIR, tax, model + ".mat"))

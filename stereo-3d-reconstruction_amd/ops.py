@@ -23,6 +23,7 @@ import torch.nn as nn
 from . import _lib
 from . import arch_spec as spec
 from ._tensors import _aligned16, _check_channel_vector, _check_input, _check_input_cl, _stream_ptr
+from .augment import augment_pair      # noqa: F401  (the augmentation's functional form lives with its config: augment.py)
 
 _LINEAR_ACTS = ("none", "relu", "sigmoid")
 
