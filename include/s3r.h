@@ -132,9 +132,16 @@ typedef enum s3r_act { S3R_ACT_NONE = 0, S3R_ACT_RELU = 1, S3R_ACT_SIGMOID = 2,
  *                      batch cannot take it.
  * (Value 1 was S3R_LAYOUT_S2D — parity-split intermediates for stride-2 consumers, bf16 and fp32 forms — through ABI 6: built,
  * bit-identical, measured slower / no gain inside the forward in rounds 2 and 3, never planned by default; removed in ABI 7.) */
-/*   S3R_LAYOUT_WINO_DH the same for the TWO-AXIS kernel (Conv3d k3 s1 p1, edge a multiple of 4): 36 plane sets
- *                      (36, B, C, n/4, n/4, n+2), set 6 a + b = depth class a, row class b of the 6 x 6 window of padded depths
- *                      4 s .. 4 s + 5 and padded rows 4 q .. 4 q + 5 (rows first, then depths).  s3r_cost_volume_forward_wino2 writes it.
+/*   S3R_LAYOUT_WINO_DH the same for the TWO-AXIS kernel (Conv3d k3 s1 p1, edge a multiple of 4): 36 plane sets of
+ *                      36 B C (n/4) (n/4) (n+2) floats, in memory (36, B, C, n/4, n+2, n/4) — depth group s, PADDED COLUMN, row
+ *                      group q, the row group fastest —, set 6 a + b = depth class a, row class b of the 6 x 6 window of padded
+ *                      depths 4 s .. 4 s + 5 and padded rows 4 q .. 4 q + 5 (rows first, then depths).  A buffer in this layout IS
+ *                      the output of s3r_cost_volume_forward_wino2, its only producer (there is no transform entry for it), and
+ *                      the consumer relies on that: C is two halves of a cost volume of edge n, masked as that call masks them,
+ *                      and the class GEMM never reads the K tiles that hold only the mask's zeros (csrc/s3r_cv_live.h).  Anything
+ *                      else written there is not read as such: a value placed in a masked region may be ignored.  The layer's
+ *                      weights must be finite: an infinite weight times a structural zero was NaN where the tile was multiplied
+ *                      and is 0 where it is left out.
  *   S3R_LAYOUT_WINO_HW the two-axis kernel's input in 2D (Conv2d k3 s1 p1, edge n a multiple of 4): (36, C, P) with the positions
  *                      of the whole batch flat, P = B (n/4)^2 rounded up to a multiple of 64, position (b, q, s); set 6 a + b =
  *                      column class a, row class b of the 6 x 6 window of padded rows 4 q .. 4 q + 5 and padded columns
@@ -330,8 +337,9 @@ int64_t s3r_conv_wino_input_elems(const s3r_conv_desc* d);
 /* ... and which layout that is: S3R_LAYOUT_WINO_H (the one-axis kernel), S3R_LAYOUT_WINO_DH (the two-axis kernel), or
  * S3R_LAYOUT_PLAIN (none: hand the layer its plain halo-padded input) */
 int s3r_conv_wino_input_layout(const s3r_conv_desc* d);
-/* the volume as the S3R_LAYOUT_WINO_DH input of the 3D convolution that consumes it: (36, B, 2C, D/4, H/4, W+2) floats,
- * bit-identical to the two-axis input transform of the padded volume; max_disp and height multiples of 4 */
+/* the volume as the S3R_LAYOUT_WINO_DH input of the 3D convolution that consumes it: 36 B 2C (D/4) (H/4) (W+2) floats, in memory
+ * (36, B, 2C, D/4, W+2, H/4) — the column outside the row group —, each value bit-identical to the two-axis input transform of the
+ * padded volume; max_disp and height multiples of 4 */
 int s3r_cost_volume_forward_wino2(const float* feat_left, const float* feat_right, float* planes, int batch, int channels,
                                   int max_disp, int height, int width, void* stream);
 

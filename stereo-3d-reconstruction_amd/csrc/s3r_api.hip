@@ -353,6 +353,9 @@ int run_wino2(const ConvCall& c, s3r::ConvParams p, int form, const HeadWork& he
     p.Hout = g2.out; p.Dout = g2.out;
     p.ncls = g2.ncls;
     p.ksplit = 1;
+    // S3R_LAYOUT_WINO_DH is what s3r_cost_volume_forward_wino2 wrote, column outside the row group (include/s3r.h): launch_conv_wino2
+    // re-aims the class GEMM at that order and leaves out the K tiles that hold the volume's structural zeros
+    p.cv_n = d->in_layout == S3R_LAYOUT_WINO_DH ? g2.out : 0;
     const int64_t x_sample = g.x_elems / d->batch;
     ps.launches = 0;
     for (int b0 = 0; b0 < d->batch; b0 += g2.bmax) {

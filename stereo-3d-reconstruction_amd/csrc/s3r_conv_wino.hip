@@ -31,6 +31,7 @@
 //   pack_wino_kernel    w[Cout][Cin][kd][3][kw]    -> Up[6][(chunk*T' + tap')*32 + c][CoutPad],  T' = kd*kw, 32-channel chunks
 //   wino_kernel / wino_dual_kernel / wino_finish_kernel: the class kernels, below
 #include "s3r_kernels.h"
+#include "s3r_cv_live.h"
 #include <cstdlib>
 
 namespace s3r {
@@ -332,7 +333,11 @@ __device__ __forceinline__ float wino_head_act(float t, int act) {
 // SEMI (two-axis convolution, below): the workgroup owns ONE depth class a of its tile and walks that class's six row classes
 // serially (plane sets / weight slabs 6 a .. 6 a + 5); the row transform runs on the registers and the four row outputs go,
 // raw, to the slab part[a][row][cout][n] for wino2s_finish_kernel to transform along D
-template <int VEC, int KIND, int WN, bool CP, bool HEAD, bool XM = false, bool SEMI = false>
+// CVL (two-axis convolution whose input is the cost volume's plane sets, p.cv_n > 0): p is launch_conv_wino2's re-aimed view — Nd = 1,
+// Nh = depth groups, Nw = the n * n / 4 positions of one, the three column taps as "depth" taps x_ds = n / 4 apart — and the K walk
+// leaves out the (chunk, tap) tiles that read structural zeros only (s3r_cv_live.h): one mask per workgroup, so the ring, the
+// counted vmcnt and the barriers see a shorter class and nothing else.  The tiles left out added w * (+0) to a finite sum: same bits
+template <int VEC, int KIND, int WN, bool CP, bool HEAD, bool XM = false, bool SEMI = false, bool CVL = false>
 __device__ __forceinline__ void wino_body(const ConvParams& p, const int bid_in, const int nwg_in, const int n_begin,
                                           const int n_end, float* __restrict__ wsmem) {
     constexpr bool DECONV = KIND == 2;
@@ -343,6 +348,7 @@ __device__ __forceinline__ void wino_body(const ConvParams& p, const int bid_in,
     static_assert(!SEMI || (KIND == 1 && !CP && !HEAD), "the semi-fused form: serial F(4,3) row classes of one depth class");
     static_assert(WN == 4 || WN == 2, "4 waves as 1 x 4 or 2 x 2");
     static_assert(!HEAD || (DECONV && !CP && WN == 2), "the fused head: serial transposed form");
+    static_assert(!CVL || (KIND == 1 && (CP || SEMI)), "live K tiles: the two-axis forms of the cost volume's consumer");
     float* As = wsmem;                                   // [WNB][WBK][64]
     constexpr int BSTG = (DECONV ? 2 : 1) * WBK * BN;    // B floats per stage (transposed: depths z and z + 1 side by side)
     float* Bs = wsmem + WNB * WBK * WBM;                 // [WNB][BSTG]
@@ -396,7 +402,24 @@ __device__ __forceinline__ void wino_body(const ConvParams& p, const int bid_in,
     const int T = DECONV ? 2 : p.T;                      // taps per class: (depth tap,) column tap
     const int chunks = p.Cin / WBK;
     const int nkt = T * chunks;                          // K tiles per class
-    const int total = NACC * nkt;
+    int nrun = nkt;                                      // ... that a class walks
+    unsigned live = 0;                                   // (CVL) bit chunk * 3 + tap: the K tile is live; the same for every class
+    if constexpr (CVL) {                                 // (the launcher keeps nkt <= 32)
+        // the tile's first and last position as (sample, depth group) g and column: Nw positions per g, Nh row groups per column (and
+        // Nh depth groups per sample), through the launch's fast divisions
+        const int last = (n0 + BN < n_end ? n0 + BN : n_end) - 1, half_c = p.Cin >> 1;
+        const int g = p.dW.div(n0), sd = g - p.dNh.div(g) * p.Nh;
+        const bool one = p.dW.div(last) == g;
+        const int w_lo = p.dNh.div(n0 - g * p.Nw), w_hi = p.dNh.div(last - g * p.Nw);
+        for (int tw = 0; tw < 3; ++tw) {
+            const bool l0 = !s3r_cv_ktile_dead_at(p.cv_n, 0, tw, one, sd, w_lo, w_hi);
+            const bool l1 = !s3r_cv_ktile_dead_at(p.cv_n, 1, tw, one, sd, w_lo, w_hi);
+            for (int cc = 0; cc < chunks; ++cc)          // (a chunk that holds channels of both halves is live when either is)
+                if ((cc * WBK < half_c && l0) || (cc * WBK + WBK > half_c && l1)) live |= 1u << (cc * 3 + tw);
+        }
+        nrun = __builtin_popcount(live);
+    }
+    const int total = NACC * nrun;
 
     int bvoff;
     {
@@ -436,6 +459,7 @@ __device__ __forceinline__ void wino_body(const ConvParams& p, const int bid_in,
     int c_cls = cls0, c_cc = 0, c_td = 0, c_tw = 0, c_tap = 0;
     int c_kt = (DECONV ? pc * NCLS + cls0 : cls0) * nkt;
     int c_a = cls0 / 3, c_b = cls0 - 3 * (cls0 / 3);     // (transposed form) the class's depth / row part
+    unsigned c_rem = live;                               // (CVL) the class's live K tiles still to fetch
 #ifdef S3R_ABLATE   // diagnostic builds only (tools/README.md): what the operand DMAs of the K loop cost the matrix pipe
     bool abl_loop = false;                               // set once the prologue's tiles are out
 #endif
@@ -447,6 +471,10 @@ __device__ __forceinline__ void wino_body(const ConvParams& p, const int bid_in,
 #else
         constexpr bool skip_a = false, skip_b = false;
 #endif
+        if constexpr (CVL) {                             // the class's next live K tile: chunk c_tap / 3, column tap c_tap % 3
+            c_tap = __builtin_ctz(c_rem);
+            c_kt = c_cls * nkt + c_tap;
+        }
         if (!skip_a) {
 #pragma unroll
             for (int q = 0; q < WNPA; ++q)
@@ -492,6 +520,15 @@ __device__ __forceinline__ void wino_body(const ConvParams& p, const int bid_in,
                     if (++c_b == 3) { c_b = 0; ++c_a; }
                 }
             }
+        } else if constexpr (CVL) {
+            const int cc = c_tap / 3;
+            const int b_base = (c_cls * p.x_cls + (cc * WBK + b_row0) * p.x_cs + (c_tap - 3 * cc) * p.x_ds) * 4;
+            if (!skip_b) {
+#pragma unroll
+                for (int q = 0; q < NPB; ++q) wdma<4 * VEC>(xrsrc, sb + q * B_LDS_STEP, bvoff, b_base + q * B_ROW_STEP * cs4);
+            }
+            c_rem &= c_rem - 1;
+            if (c_rem == 0) { c_rem = live; ++c_cls; }
         } else {
             const int b_base = (c_cls * p.x_cls + (c_cc * WBK + b_row0) * p.x_cs + c_td * p.x_ds + c_tw) * 4;
             if (!skip_b) {
@@ -534,7 +571,7 @@ __device__ __forceinline__ void wino_body(const ConvParams& p, const int bid_in,
     int cur = 0, g = 0;
     // diff (transposed form, depth part a != 1): the B fragment is the difference of the two depth tiles of the stage
     auto run_class = [&](wf32x16 (&ac)[TM], const bool diff) __attribute__((always_inline)) {
-        for (int kt = 0; kt < nkt; ++kt, ++g) {
+        for (int kt = 0; kt < nrun; ++kt, ++g) {
             const bool more = g + WNB - 1 < total;
             if (more) issue(cur == 0 ? WNB - 1 : cur - 1);        // into the stage tile g - 1 was read from
             const float* a = As + cur * WBK * WBM + a_off;
@@ -746,10 +783,10 @@ __device__ __forceinline__ void wino_body(const ConvParams& p, const int bid_in,
 
 // registers: six classes of one 32 x 32 tile = 96 accumulators (109 in all: four workgroups per CU), nine = 144 (three per CU);
 // the class-parallel form 16
-template <int VEC, int KIND, int WN, bool CP, bool HEAD, bool XM = false, bool SEMI = false>
+template <int VEC, int KIND, int WN, bool CP, bool HEAD, bool XM = false, bool SEMI = false, bool CVL = false>
 __global__ __launch_bounds__(256, (CP || KIND == 1 ? 4 : 3)) void wino_kernel(const ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) float wsmem[];
-    wino_body<VEC, KIND, WN, CP, HEAD, XM, SEMI>(p, blockIdx.x, gridDim.x, p.n_begin, p.n_end, wsmem);
+    wino_body<VEC, KIND, WN, CP, HEAD, XM, SEMI, CVL>(p, blockIdx.x, gridDim.x, p.n_begin, p.n_end, wsmem);
 }
 
 // bulk (serial form, positions [n_begin, n_cut)) + remainder (class-parallel form, positions [n_cut, n_end)) in ONE launch: the
@@ -1163,6 +1200,13 @@ __device__ __forceinline__ void wino2_zero_out(float* __restrict__ dst, int coun
     }
 }
 
+// a group g of one (sample, depth group) of a 3D two-axis layer -> its row group and column: (row group, column), or — the cost
+// volume's consumer, p.cv_n — (column, row group)
+__device__ __forceinline__ void wino2_group_pos(const ConvParams& p, int g, int& sh, int& pw) {
+    if (p.cv_n) { pw = p.dNh.div(g); sh = g - pw * p.Nh; }
+    else { sh = p.dW.div(g); pw = g - sh * p.Nw; }
+}
+
 // 3D, semi-fused form: one workgroup per (cout, SUB consecutive (sample, depth group) pairs — as many as give its 256 threads a
 // group each): slabs [a][row][Cout][npad] (the row transform already applied by the class kernel) -> 4 output slices per pair:
 // A^T along D, folded BN + activation.  y: halo-padded, y_hs = W + 2 halo, y_ds = a slice
@@ -1186,8 +1230,8 @@ __global__ __launch_bounds__(256) void wino2s_finish_kernel(const ConvParams p, 
         for (int t = tid; t < nsub * G; t += 256) {
             const int sub = p.dHW.div(t);
             const int g = t - sub * G;
-            const int sh = p.dW.div(g);
-            const int pw = g - sh * p.Nw;
+            int sh, pw;
+            wino2_group_pos(p, g, sh, pw);
             const int r = r0 + sub;
             const int sd = r - dNd.div(r) * p.Nd;
             const int n = r0 * G + t;                                  // (slabs blocked by (cout, 64-position tile): wino_body, SEMI)
@@ -1249,8 +1293,8 @@ __global__ __launch_bounds__(256) void wino2_finish_flat_kernel(const ConvParams
         int rem = n - b * S;
         const int sd = p.dHW.div(rem);
         rem -= sd * p.Nh * p.Nw;
-        const int sh = p.dW.div(rem);
-        const int pw = rem - sh * p.Nw;
+        int sh, pw;
+        wino2_group_pos(p, rem, sh, pw);
         const float* __restrict__ src = p.part + ((size_t)mrow * (npad >> 6) + (n >> 6)) * (N * N * 64) + (n & 63);     // (blocked slabs)
         float t[N][M];                                                   // [depth class][output row]
 #pragma unroll
@@ -1547,8 +1591,8 @@ __global__ __launch_bounds__(256) void wino_handoff_kernel(const ConvParams p, c
                 const int n = b * S + g;
                 const int sd = p.dHW.div(g);
                 g -= sd * p.Nh * p.Nw;
-                const int sh = p.dW.div(g);
-                const int pw = g - sh * p.Nw;
+                int sh, pw;
+                wino2_group_pos(p, g, sh, pw);
                 const float* __restrict__ src = p.part + ((size_t)mrow * (npad >> 6) + (n >> 6)) * (N * N * 64) + (n & 63);
                 float tt[N][M];                                          // [depth class][output row]
 #pragma unroll
@@ -1804,6 +1848,20 @@ hipError_t launch_conv_wino2(ConvParams p, int ax, int form, bool to_v, hipStrea
         return hipGetLastError();
     }
     if (p.y_ds != p.y_hs * p.y_hs || p.y_cs != (p.Dout + 2 * halo) * p.y_ds) return hipErrorInvalidValue;
+    // The cost volume's plane sets (p.cv_n; (.., depth group, padded column, row group)): p stays the finish kernels' view, the class
+    // GEMM walks q — one flat run of n * n / 4 positions per depth group, the three column taps n / 4 elements apart as "depth" taps
+    // (tap order, packed weights and so the K order are the layer's own) — and leaves out the dead K tiles where a 32-bit mask holds a class's
+    ConvParams q = p;
+    const bool cvl = p.cv_n > 0;
+    if (cvl) {
+        if (ax != 0 || p.kw != 3 || p.Nw != p.cv_n || p.Nh * 4 != p.cv_n || p.Nd != p.Nh || (p.Cin & 1)) return hipErrorInvalidValue;
+        q.Nd = 1; q.Nh = p.Nd; q.Nw = p.Nw * p.Nh;
+        q.dS = q.dHW = FastDiv((unsigned)(q.Nh * q.Nw)); q.dW = FastDiv((unsigned)q.Nw);
+        q.kd = 3; q.kw = 1; q.T = 3;
+        q.x_hs = p.x_hs * p.Nh; q.x_ds = p.Nh;
+        p.dNh = q.dNh = FastDiv((unsigned)p.Nh);      // (row groups per column = depth groups per sample: p.Nd == p.Nh)
+    }
+    const bool cvl_skip = cvl && 3 * (p.Cin / WBK) <= 32;
     if (form == 1) {
         // (only this form's finish kernel stages output slices in LDS: the class-parallel form's flat kernel has no edge limit)
         const int M = wino2_outputs(ax), G = p.Nh * p.Nw;
@@ -1816,8 +1874,9 @@ hipError_t launch_conv_wino2(ConvParams p, int ax, int form, bool to_v, hipStrea
         const long long items = (long long)p.Cout * ((p.B * p.Nd + SUB - 1) / SUB);
         const dim3 fgrid((unsigned)(items < 32768 ? items : 32768));
         const dim3 grid(p.m_tiles * n_tiles * 6);
-        if (p.Nw % 4 == 0) hipLaunchKernelGGL((wino_kernel<4, 1, 2, false, false, false, true>), grid, dim3(256), lds, stream, p);
-        else hipLaunchKernelGGL((wino_kernel<1, 1, 2, false, false, false, true>), grid, dim3(256), lds, stream, p);
+        if (cvl_skip) hipLaunchKernelGGL((wino_kernel<4, 1, 2, false, false, false, true, true>), grid, dim3(256), lds, stream, q);
+        else if (q.Nw % 4 == 0) hipLaunchKernelGGL((wino_kernel<4, 1, 2, false, false, false, true>), grid, dim3(256), lds, stream, q);
+        else hipLaunchKernelGGL((wino_kernel<1, 1, 2, false, false, false, true>), grid, dim3(256), lds, stream, q);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         AuxScope aux(stream, 4.0 * (double)p.Cout * (24.0 * n_tiles * WCN + (double)p.B * p.y_cs));      // (slabs in, padded output out)
@@ -1826,8 +1885,9 @@ hipError_t launch_conv_wino2(ConvParams p, int ax, int form, bool to_v, hipStrea
         return hipGetLastError();
     }
     const dim3 grid(p.m_tiles * n_tiles * p.ncls);
-    if (p.Nw % 4 == 0) hipLaunchKernelGGL((wino_kernel<4, 1, 2, true, false>), grid, dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL((wino_kernel<1, 1, 2, true, false>), grid, dim3(256), lds, stream, p);
+    if (cvl_skip) hipLaunchKernelGGL((wino_kernel<4, 1, 2, true, false, false, false, true>), grid, dim3(256), lds, stream, q);
+    else if (q.Nw % 4 == 0) hipLaunchKernelGGL((wino_kernel<4, 1, 2, true, false>), grid, dim3(256), lds, stream, q);
+    else hipLaunchKernelGGL((wino_kernel<1, 1, 2, true, false>), grid, dim3(256), lds, stream, q);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (launches) *launches = 2;

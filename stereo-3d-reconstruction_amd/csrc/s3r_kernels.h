@@ -140,6 +140,12 @@ struct ConvParams {
     // k4 p0, 2 [x | Dh | Dd | Ddh] of a transposed Winograd layer; y_hs / y_ds / y_cs / y_org still describe the halo-padded plain
     // output, which is the consumer's input geometry
     int out_mode;
+    // > 0: x is the S3R_LAYOUT_WINO_DH plane sets the cost-volume writer produced for a volume of this edge, (36, B, 2C, n/4, n+2, n/4):
+    // positions run (sample, depth group, column, row group) — the class GEMM walks a re-aimed view of them (launch_conv_wino2) and
+    // skips the K tiles s3r_cv_live.h calls dead, the finish kernels decode a group as (column, row group); dNh: / (n / 4), the row
+    // groups per column and the depth groups per sample
+    int cv_n;
+    FastDiv dNh;
 };
 
 // The residue classes of a general ConvTranspose (s3r_general.hip) as ONE launch of the direct kernel: workgroup ranges of a class
@@ -226,7 +232,7 @@ hipError_t launch_conv_wino2(ConvParams p, int ax, int form, bool to_v, hipStrea
 // prod: 0 / 1 the class slabs of a class-parallel two-axis Conv3d (ax 0 / 1), 2 those of a class-parallel transposed Winograd layer,
 // 3 the split-K partial slabs of a direct convolution; cons: see ConvParams::out_mode; npad: positions per slab row
 hipError_t launch_wino_handoff(const ConvParams& p, int prod, int cons, int npad, hipStream_t stream);
-// the cost volume written as the 36 two-axis plane sets of its halo-1 padded form: V[36][B][2C][(D)/4][H/4][W+2]
+// the cost volume written as the 36 two-axis plane sets of its halo-1 padded form, column outside the row group: V[36][B][2C][D/4][W+2][H/4]
 hipError_t launch_cost_volume_wino2(const float* fl, const float* fr, float* V, int B, int C, int D, int H, int W, hipStream_t s);
 int wino_bk();                      // channels per K tile of the Winograd kernels (Cin must be a multiple)
 // Winograd F(2,2) along D and H inside the parity classes of ConvTranspose3d(k4 s2 p1); D = [Dh] or (three) [Dh | Dd | Ddh]

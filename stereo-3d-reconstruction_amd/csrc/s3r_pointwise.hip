@@ -363,7 +363,9 @@ hipError_t launch_cost_volume_wino(const float* fl, const float* fr, float* V, i
 }
 
 // ... and as the 36 TWO-AXIS plane sets (F(4,3) along D and H: s3r_conv_wino.hip, wino2_input_kernel, S3R_LAYOUT_WINO_DH):
-// V[6 a + b][bb][ch][sd][sh][wp] from the 6 x 6 window of padded depths 4 sd .. 4 sd + 5 and padded rows 4 sh .. 4 sh + 5 at column
+// V[6 a + b][bb][ch][sd][wp][sh] — the column OUTSIDE the row group, so that 64 consecutive positions of the consumer's class GEMM
+// are whole columns of every row group and the volume's masked triangle forms whole K tiles it can leave out (s3r_cv_live.h) —
+// from the 6 x 6 window of padded depths 4 sd .. 4 sd + 5 and padded rows 4 sh .. 4 sh + 5 at column
 // wp of the halo-1 volume — rows first, then depths, through the same wino_rows_to_classes: bit-identical to the transform
 // kernel applied to the padded volume.  One workgroup per (b, c); a thread per (sd, sh, wp) and slab half.  Small batches
 // (gridDim.y = 2 or 2 SD): a workgroup per (b, c, slab half[, depth group]) — 32 workgroups of 12 serial passes are 46 us at B = 1.
@@ -393,10 +395,10 @@ __global__ __launch_bounds__(256) void cost_volume_wino2_kernel(const float* __r
     for (int half = half0; half < half1; ++half) {       // the L - R(shifted) slab, then the R - L(shifted) slab
         float* __restrict__ o = V + ((size_t)b * 2 * C + half * C + c) * run;
         for (int e = e0 + threadIdx.x; e < e1; e += 256) {
-            const int sd = dPlane.div(e);                // e / (SH*Wp)
+            const int sd = dPlane.div(e);                // e / (Wp*SH)
             const int rem = e - sd * ds;
-            const int sh = dRow.div(rem);                // rem / Wp
-            const int wp = rem - sh * Wp;
+            const int wp = dRow.div(rem);                // rem / SH
+            const int sh = rem - wp * SH;
             const int w = wp - 1;
             float t[6][6];                               // [depth][row class]
 #pragma unroll
@@ -433,7 +435,7 @@ hipError_t launch_cost_volume_wino2(const float* fl, const float* fr, float* V, 
     const long long cls_stride = (long long)B * 2 * C * SD * SH * Wp;
     const int ny = B * C <= 128 ? 2 * SD : B * C <= 512 ? 2 : 1;      // (same bits: the split only re-distributes elements)
     hipLaunchKernelGGL(cost_volume_wino2_kernel, dim3(B * C, ny), dim3(256), lds, s, fl, fr, V, C, D, H, W, cls_stride,
-                       FastDiv((unsigned)(SH * Wp)), FastDiv((unsigned)Wp));
+                       FastDiv((unsigned)(SH * Wp)), FastDiv((unsigned)SH));
     return hipGetLastError();
 }
 

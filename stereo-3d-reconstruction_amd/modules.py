@@ -586,15 +586,19 @@ class CostVolume(nn.Module):
     @torch.no_grad()
     def forward_wino2(self, feat_left: torch.Tensor, feat_right: torch.Tensor) -> torch.Tensor:
         """The same hand-off for a decoder whose first 3D conv runs the TWO-AXIS Winograd kernel: the 36 F(4,3) x F(4,3) plane
-        sets of the halo-1 padded volume, (36,B,2C,D/4,H/4,W+2), bit-identical to the consumer's own input transform."""
+        sets of the halo-1 padded volume, (36,B,2C,D/4,H/4,W+2), each value bit-identical to the consumer's own input transform.  In
+        memory the column lies OUTSIDE the row group, (36,B,2C,D/4,W+2,H/4) — what S3R_LAYOUT_WINO_DH is — so the tensor handed back
+        is a transposed VIEW of the resident buffer (the way the bf16 modules hand each other logical views of channels-last buffers):
+        Decoder.forward_padded(in_layout=LAYOUT_WINO_DH) takes it as it is; its first layer skips the K tiles that hold the volume's
+        structural zeros."""
         fl = _check_input(feat_left, "feat_left", feat_left.shape[1:])
         fr = _check_input(feat_right, "feat_right", feat_left.shape[1:])
         B, Cc, H, W = fl.shape
-        shape = (36, B, 2 * Cc, self.max_disp // 4, H // 4, W + 2)
+        shape = (36, B, 2 * Cc, self.max_disp // 4, W + 2, H // 4)
         planes = self._resident("_planes", shape, fl.device)
         _lib.check(_lib.load().s3r_cost_volume_forward_wino2(fl.data_ptr(), fr.data_ptr(), planes.data_ptr(), B, Cc,
                                                              self.max_disp, H, W, _stream_ptr(fl.device)), "cost_volume (wino2)")
-        return planes
+        return planes.transpose(-1, -2)
 
     def forward_for(self, consumer, feat_left: torch.Tensor, feat_right: torch.Tensor):
         """(volume, in_layout) in whatever form `consumer` (a Decoder / VolumeEncoder) reads fastest for this batch."""
@@ -637,8 +641,11 @@ def _check_wino_planes(v: torch.Tensor, layout: int = _lib.LAYOUT_WINO_H) -> tor
     else:
         ncls, want = 6, (2 * spec.FEAT_C, spec.MAX_DISP + 2, spec.FEAT_HW // 4, spec.FEAT_HW + 2)
     if not isinstance(v, torch.Tensor) or not v.is_cuda or v.dtype != torch.float32 or v.dim() != 6 or v.shape[0] != ncls or \
-            tuple(v.shape[2:]) != want or not v.is_contiguous():
+            tuple(v.shape[2:]) != want or (layout != _lib.LAYOUT_WINO_DH and not v.is_contiguous()):
         raise RuntimeError(f"transformed volume must be a contiguous float32 HIP tensor ({ncls}, B, {', '.join(map(str, want))})")
+    if layout == _lib.LAYOUT_WINO_DH:      # in memory (.., W+2, H/4): CostVolume.forward_wino2's view passes through, anything else is copied once
+        phys = v.transpose(-1, -2)
+        return (phys if phys.is_contiguous() else phys.contiguous()).transpose(-1, -2)
     return v
 
 
@@ -658,7 +665,7 @@ class _VolumeChain(_HipChain):
     def _run_padded(self, volume_padded: torch.Tensor, halo: int, in_layout: int, upto: Optional[str] = None) -> torch.Tensor:
         """The chain on the halo-padded volume CostVolume.forward_padded produced (no pad copy; bf16: physical
         (B,D+2h,H+2h,W+2h,2C)), or (in_layout = LAYOUT_WINO_H / LAYOUT_WINO_DH) on the transformed planes CostVolume.forward_wino /
-        forward_wino2 produced."""
+        forward_wino2 produced (LAYOUT_WINO_DH: exactly that call's output — the first layer relies on the cost volume's mask)."""
         if in_layout in (_lib.LAYOUT_WINO_H, _lib.LAYOUT_WINO_DH):
             return self._run(_check_wino_planes(volume_padded, in_layout), upto, in_halo=1, in_layout=in_layout)
         n = (spec.MAX_DISP + 2 * halo, spec.FEAT_HW + 2 * halo, spec.FEAT_HW + 2 * halo)
