@@ -50,6 +50,8 @@
  *                                           and learning rate on the device                (README.md:36,77)
  *   s3r_augment_pair (+ its scratch query)  the input augmentation of `python3 runner.py` (training) on 8-bit stereo renders, the
  *                                           disparity maps shifted along; the transform set is INVENTED by this build (README.md:36,77)
+ *   s3r_voxel_surface_points (+ its         the ground-truth clouds of `python3 runner.py --variant point` on a dataset tree: points drawn on
+ *   scratch query)                          the exposed faces of the 32^3 occupancy grids; the sampling rule is INVENTED by this build (README.md:36,77)
  *
  * Conventions
  *   - every tensor is fp32, contiguous, NCHW / NCDHW, resident in device memory owned by the caller;
@@ -92,8 +94,8 @@ extern "C" {
  * query) likewise; s3r_cost_volume_backward likewise; s3r_batchnorm_train_forward and s3r_batchnorm_train_backward (+ their scratch queries)
  * likewise; s3r_stem_backward (+ its scratch query) likewise; s3r_disparity_soft_backward, s3r_disparity_loss_forward and
  * s3r_disparity_loss_backward likewise; s3r_optim_step, s3r_optim_state_init, s3r_optim_set_lr and s3r_optim_scratch_elems (with their two
- * structs) likewise; s3r_augment_pair and s3r_augment_scratch_elems (with their struct) likewise: new entry points only, the version
- * stays 8. */
+ * structs) likewise; s3r_augment_pair and s3r_augment_scratch_elems (with their struct) likewise; s3r_voxel_surface_points and
+ * s3r_voxel_surface_points_scratch_elems likewise: new entry points only, the version stays 8. */
 #define S3R_ABI_VERSION 8
 
 typedef enum s3r_status {
@@ -975,6 +977,49 @@ int s3r_augment_pair(const s3r_augment_desc* d, const uint8_t* left, const uint8
                      const float* disp_left, const float* disp_right, float* out_left, float* out_right,
                      float* out_disp_left, float* out_disp_right, int batch, int height, int width,
                      float* scratch, int64_t scratch_elems, void* hip_stream);
+
+/* Ground-truth point clouds from occupancy grids: n_points points per sample, drawn on the exposed faces of the grid's occupied voxels.
+ * It is how Stereo2Point trains and validates on a StereoShapeNet tree, which holds 32^3 grids and no clouds.  Deterministic, atomics-free,
+ * nothing drawn or read on the host: a sample's bits are a function of (seed, sample_ids[b], its grid, threshold, n_points) only — not of
+ * its batch, its position in the batch, an address, the scratch contents on entry or the launch shape — and a captured call replays with
+ * fresh clouds from the grids and ids in the device buffers.  The sampling rule is INVENTED by this build (the reference's own Stereo2Point
+ * code is on unmounted branches), to be overwritten from the reference the day it is mounted.
+ *
+ * Tensors.  occupancy (B, D, H, W) fp32.  sample_ids (B) int64 ON THE DEVICE (8-byte aligned, as s3r_augment_pair reads them).  points
+ * (B, n_points, 3) fp32, 4-byte aligned.  n_faces (B) int32, or NULL.
+ *
+ * Occupancy and faces.  A voxel is occupied iff v > threshold: a NaN is empty.  Face f = 2 a + side of voxel (i0, i1, i2): a is the axis
+ * (0 = D, 1 = H, 2 = W), side 0 faces the lower neighbour along a, side 1 the upper one.  A face is exposed iff its voxel is occupied and
+ * that neighbour is outside the grid or empty.  Exposed faces are numbered in ascending e = 6 * ((i0 * H + i1) * W + i2) + f; N is their
+ * count for the sample, written to n_faces[b].
+ *
+ * Draws.  Point j of sample b takes Philox4x32-10 with s3r_augment_pair's multipliers, Weyl constants and u(w) = (float)(w >> 8) * 2^-24:
+ * key = (seed low, seed high), counter = (id low, id high, purpose 0x100, j) with id = sample_ids[b]; w0..w3 are its output words.
+ * k = (uint64)w0 * N >> 32 is the index of the point's face in the numbering above.  A prefix of a larger n_points is the smaller cloud.
+ *
+ * Coordinates.  inv_c = 1.f / (float)size_c (correctly rounded).  On the normal axis a:  t = (float)(i_a + side).  On the two in-plane
+ * axes, in ascending axis order, with u(w1) then u(w2):  t = (float)i_c + u.  On every axis:  t = t * inv_c;  p_c = t - 0.5f.  Every
+ * operation is rounded on its own (nothing contracted into a fused multiply-add).  The cloud lies in [-0.5, 0.5]^3 and component c of a
+ * point is grid axis c.  A cubic grid is sampled uniformly by area; a non-cubic one uniformly by face count (its faces differ in area).
+ * Empty grid: with N = 0 every point of that sample is (+0.0, +0.0, +0.0) and n_faces[b] = 0.
+ * The result is integers plus three rounded operations per component: it contains no floating-point sum, so any launch structure gives
+ * the same bits.
+ *
+ * scratch: s3r_voxel_surface_points_scratch_elems(batch, depth, height, width) floats = B (17 ceil(D H W / 64) + 1) (per 64-voxel chunk
+ * its face count, then prefix, and 64 mask bytes; per sample N); its contents on entry do not matter.  The query returns S3R_ERR_INVALID
+ * for the geometries the call refuses.
+ * Refused with S3R_ERR_INVALID and a message, host-side, before anything is enqueued: a NULL occupancy, sample_ids or points; batch or
+ * n_points <= 0; an edge outside 1..256; D H W > 2^21; batch * n_points * 3 >= 2^31; a scratch of 2^31 elements or more; a non-finite
+ * threshold; scratch NULL or scratch_elems below the query; points, n_faces or scratch overlapping an input or each other.
+ * Launches: three — the exposure masks with per-chunk face counts, one workgroup per sample for the prefix and N, one lane per point.
+ * Every node is a kernel (no memset, no copy), there are no atomics and nothing is read on the host.
+ * `hip_stream` is the hipStream_t of the Conventions above (NULL = the default stream; work is enqueued, not waited for; the call can be
+ * stream-captured into a HIP graph and replayed on new grids and ids in the same buffers).
+ * Profiler: no record (the call is meant to be captured, and the event profiler must be off while capturing). */
+int64_t s3r_voxel_surface_points_scratch_elems(int batch, int depth, int height, int width);
+int s3r_voxel_surface_points(const float* occupancy, float threshold, const int64_t* sample_ids, uint64_t seed,
+                             float* points, int32_t* n_faces, int batch, int depth, int height, int width,
+                             int n_points, float* scratch, int64_t scratch_elems, void* hip_stream);
 
 /* Kernel-level profiler: when enabled, every kernel the library launches is bracketed by HIP events
  * on the launch stream.  s3r_profile_read synchronises those events and returns, per launch, the

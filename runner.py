@@ -6,6 +6,7 @@
     python -m torch.distributed.run --nproc-per-node 8 runner.py --test ...   (or under an external launcher)
 
     python3 runner.py --train --out runs/a [--dataset-root ... | --data x.npz] [--resume runs/a/last.pth]
+    python3 runner.py --train|--test --variant point --dataset-root ...   (ground-truth clouds drawn from the tree's 32^3 grids)
 
 `--test` evaluates and `--train` trains (s3r.train.fit: one GPU, fp32; deterministic on-device augmentation, the HIP losses and
 optimizer step, validation through the --test path, checkpoints that carry the optimizer; one JSON line per epoch).  `python3
@@ -63,7 +64,10 @@ def main():
                     help="temperature of the soft read-out (default: s3r.DISPARITY_TEMPERATURE)")
     ap.add_argument("--variant", default="voxel", choices=["voxel", "point"],
                     help="voxel: Stereo2Voxel + IoU (default); point: Stereo2Point + Chamfer distance (.npz key `points`, "
-                         "(N,M,3); synthetic clouds otherwise)")
+                         "(N,M,3), or clouds drawn on the device from `volume` / the tree's grids; synthetic clouds otherwise)")
+    ap.add_argument("--cloud-points", type=int, default=2048,
+                    help="--variant point on occupancy grids: points per ground-truth cloud (s3r.voxel_surface_points)")
+    ap.add_argument("--cloud-seed", type=int, default=0, help="--variant point on occupancy grids: the seed of the clouds")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16"], help="fp32 (exact-fp32 MFMA) or the bf16 MFMA path")
     ap.add_argument("--samples", type=int, default=64, help="synthetic eval list length")
     ap.add_argument("--batch", type=int, default=32)
@@ -213,22 +217,30 @@ def main():
         return {"collective_backend": args.backend, "rccl_version": rccl, "n_ranks_seen": int(one.item())}
 
     if args.variant == "point":
+        cloud_kw = dict(cloud_points=args.cloud_points, cloud_seed=args.cloud_seed)
         if args.dataset_root:
-            sys.exit("runner.py --variant point reads an .npz (left, right, points) or synthetic data, not a dataset tree")
-        if args.data:
-            z = np.load(args.data)
-            left, right, clouds = renders(z["left"]), renders(z["right"]), torch.from_numpy(z["points"]).float()
+            ds = s3r.data.StereoShapeNet(args.dataset_root, render_dtype=rdt)
+            res = timed(s3r.evaluate.test_point_dataset, model, ds, batch=args.batch, device=dev, workers=args.workers, **cloud_kw)
+            left = None
         else:
-            left, right, _ = s3r.evaluate.synthetic_eval_set(args.samples, args.seed, rdt)
-            clouds = torch.rand(args.samples, 2048, 3, generator=torch.Generator().manual_seed(args.seed)) - 0.5
-        res = timed(s3r.evaluate.test_point_net, model, left, right, clouds, batch=args.batch, device=dev)
+            if args.data:
+                z = np.load(args.data)
+                left, right = renders(z["left"]), renders(z["right"])
+                clouds = torch.from_numpy(z["points" if "points" in z.files else "volume"]).float()
+            else:
+                left, right, _ = s3r.evaluate.synthetic_eval_set(args.samples, args.seed, rdt)
+                clouds = torch.rand(args.samples, 2048, 3, generator=torch.Generator().manual_seed(args.seed)) - 0.5
+            res = timed(s3r.evaluate.test_point_net, model, left, right, clouds, batch=args.batch, device=dev, **cloud_kw)
         info = dist_info()
         if rank == 0:
             print(json.dumps(dict({"samples": res["samples"], "n_gpus": world, "mean_chamfer": round(res["mean_chamfer"], 8),
                                    "precision": args.precision, "eval_pairs_per_s": rate(res["samples"]),
-                                   "renders": str(left.dtype).replace("torch.", ""),
+                                   "renders": rdt if left is None else str(left.dtype).replace("torch.", ""),
                                    "weights": args.weights or f"seeded random init (seed {args.seed})",
-                                   "data": args.data or "synthetic"}, **info)))
+                                   "data": args.dataset_root or args.data or "synthetic"},
+                                  **({"per_taxonomy": {k: {"samples": v["samples"], "mean_chamfer": round(v["mean_chamfer"], 8)}
+                                                       for k, v in res["per_taxonomy"].items()}} if "per_taxonomy" in res else {}),
+                                  **info)))
         if dist_on:
             dist.destroy_process_group()
         return
@@ -294,15 +306,13 @@ def train_main(args):
     model.to(dev)
 
     if args.dataset_root:
-        if args.variant == "point":
-            sys.exit("runner.py --variant point reads an .npz (left, right, points) or synthetic data, not a dataset tree")
         full = s3r.data.StereoShapeNet(args.dataset_root, with_disparity=args.disparity, render_channels=4 if args.augment == "default" else 3)
         n = len(full)
     else:
         if args.data:
             z = np.load(args.data)
             fields = [torch.from_numpy(z["left"]), torch.from_numpy(z["right"]),
-                      torch.from_numpy(z["points" if args.variant == "point" else "volume"]).float()]
+                      torch.from_numpy(z["points" if args.variant == "point" and "points" in z.files else "volume"]).float()]
             if fields[0].dtype != torch.uint8:
                 sys.exit("runner.py --train reads 8-bit renders: the .npz arrays left / right must be uint8")
             if "disp_left" in z.files and "disp_right" in z.files and tuple(z["disp_left"].shape[1:]) == tuple(fields[0].shape[2:]):
@@ -324,7 +334,8 @@ def train_main(args):
     cfg = T.TrainConfig(variant=args.variant, epochs=args.epochs, batch=args.batch, lr=args.lr, optimizer=args.optimizer,
                         milestones=tuple(int(m) for m in args.milestones.split(",") if m.strip()), gamma=args.gamma,
                         augment=s3r.AugmentConfig.default(args.seed) if args.augment == "default" else s3r.AugmentConfig.identity(args.seed),
-                        disparity_weight=1.0 if with_disp else 0.0, out_dir=args.out, resume=args.resume, seed=args.seed, workers=args.workers)
+                        disparity_weight=1.0 if with_disp else 0.0, out_dir=args.out, resume=args.resume, seed=args.seed, workers=args.workers,
+                        cloud_points=args.cloud_points, cloud_seed=args.cloud_seed)
     res = T.fit(model, train_set, val_set, cfg, log=T.json_line)
     print(json.dumps({"done": True, "epochs": res["epoch"], "steps": res["step"], "best": res["best"], "checkpoint": res["checkpoint"],
                       "train_samples": len(train_set), "val_samples": 0 if val_set is None else len(val_set)}))

@@ -148,6 +148,9 @@ SIGNATURES = {
     "s3r_augment_scratch_elems": (C.c_int64, [C.POINTER(AugmentDesc), C.c_int, C.c_int, C.c_int]),
     "s3r_augment_pair": (C.c_int, [C.POINTER(AugmentDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "s3r_voxel_surface_points_scratch_elems": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "s3r_voxel_surface_points": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "s3r_profile_enable": (C.c_int, [C.c_int]),
     "s3r_profile_reset": (C.c_int, []),
     "s3r_profile_detail": (C.c_int, [C.c_int]),

@@ -1609,4 +1609,56 @@ int s3r_augment_pair(const s3r_augment_desc* d, const uint8_t* left, const uint8
     return S3R_OK;
 }
 
+// ---------------------------------------------------------------- surface point clouds (s3r_surface_points.hip)
+namespace {
+
+// the geometry's own checks, shared by the query and the call
+int surface_shape(int batch, int depth, int height, int width) {
+    if (batch <= 0) return fail(S3R_ERR_INVALID, "surface points: batch = %d must be positive", batch);
+    if (depth < 1 || depth > 256 || height < 1 || height > 256 || width < 1 || width > 256)
+        return fail(S3R_ERR_INVALID, "surface points: the grid's edges (%d, %d, %d) must be in 1..256", depth, height, width);
+    const int64_t V = (int64_t)depth * height * width;
+    if (V > (int64_t)1 << 21) return fail(S3R_ERR_INVALID, "surface points: depth * height * width = %lld must be at most 2^21", (long long)V);
+    if (s3r::surface_points_scratch(batch, V) >= kMaxElems)
+        return fail(S3R_ERR_INVALID, "surface points: the scratch of the call has 2^31 elements or more: split the batch");
+    return S3R_OK;
+}
+
+}  // namespace
+
+int64_t s3r_voxel_surface_points_scratch_elems(int batch, int depth, int height, int width) {
+    int rc = surface_shape(batch, depth, height, width);
+    if (rc) return rc;
+    return s3r::surface_points_scratch(batch, (int64_t)depth * height * width);
+}
+
+int s3r_voxel_surface_points(const float* occupancy, float threshold, const int64_t* sample_ids, uint64_t seed, float* points,
+                             int32_t* n_faces, int batch, int depth, int height, int width, int n_points, float* scratch,
+                             int64_t scratch_elems, void* hip_stream) {
+    int rc = surface_shape(batch, depth, height, width);
+    if (rc) return rc;
+    if (!occupancy || !sample_ids || !points) return fail(S3R_ERR_INVALID, "surface points: null occupancy, sample_ids or points");
+    if (n_points <= 0) return fail(S3R_ERR_INVALID, "surface points: n_points = %d must be positive", n_points);
+    if ((int64_t)batch * n_points * 3 >= kMaxElems)
+        return fail(S3R_ERR_INVALID, "surface points: batch * n_points * 3 must be below 2^31: split the batch");
+    if (!std::isfinite(threshold)) return fail(S3R_ERR_INVALID, "surface points: the threshold must be finite");
+    const int64_t V = (int64_t)depth * height * width, need = s3r::surface_points_scratch(batch, V);
+    if (!scratch || scratch_elems < need)
+        return fail(S3R_ERR_INVALID, "surface points: needs %lld floats of scratch (s3r_voxel_surface_points_scratch_elems), got %lld",
+                    (long long)need, scratch ? (long long)scratch_elems : 0ll);
+    const AugSpan outs[3] = {{points, 12 * (int64_t)batch * n_points, "points"}, {n_faces, 4 * (int64_t)batch, "n_faces"},
+                             {scratch, 4 * need, "scratch"}};
+    const AugSpan ins[2] = {{occupancy, 4 * (int64_t)batch * V, "occupancy"}, {sample_ids, 8 * (int64_t)batch, "sample_ids"}};
+    for (int i = 0; i < 3; ++i) {
+        for (int j = i + 1; j < 3; ++j)
+            if (augment_overlap(outs[i], outs[j])) return fail(S3R_ERR_INVALID, "surface points: %s and %s overlap", outs[i].name, outs[j].name);
+        for (int j = 0; j < 2; ++j)
+            if (augment_overlap(outs[i], ins[j])) return fail(S3R_ERR_INVALID, "surface points: %s overlaps the input %s", outs[i].name, ins[j].name);
+    }
+    hipError_t e = s3r::launch_surface_points(occupancy, threshold, sample_ids, seed, points, n_faces, batch, depth, height, width, n_points,
+                                              scratch, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "surface points launch");
+    return S3R_OK;
+}
+
 }  // extern "C"

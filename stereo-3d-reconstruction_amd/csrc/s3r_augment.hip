@@ -14,6 +14,7 @@
 // The mean luma is summed in s3r_ordered.h's order with the two views as the B = 2 rows of one pair.
 // Launches: [augment_luma_kernel + augment_mean_kernel, only with contrast] + augment_apply_kernel.  No LDS, no barrier, no atomics.
 #include "s3r_ordered.h"
+#include "s3r_philox.h"
 #include "../../include/s3r.h"
 
 namespace s3r {
@@ -31,22 +32,6 @@ struct AugArgs {
     long long S;                             // H W
     long long nch;                           // chunks(S)
 };
-
-struct Words { unsigned w[4]; };
-
-__device__ __forceinline__ Words philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1;
-        c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return Words{{c0, c1, c2, c3}};
-}
-
-__device__ __forceinline__ float aug_unit(unsigned w) { return (float)(w >> 8) * 5.9604644775390625e-8f; }      // 2^-24: exact
 
 __device__ __forceinline__ float aug_range(float u, float lo, float hi) {
 #pragma clang fp contract(off)

@@ -408,6 +408,13 @@ hipError_t launch_augment_pair(const ::s3r_augment_desc* d, const uint8_t* left,
                                const float* disp_l, const float* disp_r, float* out_l, float* out_r, float* out_dl, float* out_dr, int B,
                                int H, int W, float* scratch, hipStream_t s);
 
+// s3r_surface_points.hip: ground-truth clouds drawn on the exposed faces of occupancy grids (include/s3r.h,
+// s3r_voxel_surface_points): exposure masks + chunk counts, one scan per sample, one lane per point; surface_points_scratch is the
+// floats it needs: B (17 ceil(D H W / 64) + 1)
+long long surface_points_scratch(int B, long long V);
+hipError_t launch_surface_points(const float* occ, float threshold, const int64_t* ids, uint64_t seed, float* points, int32_t* n_faces,
+                                 int B, int D, int H, int W, int n_points, float* scratch, hipStream_t s);
+
 #if defined(__HIPCC__)
 // Winograd F(4, 3) input transform along one axis (s3r_conv_wino.hip): the six class values of six consecutive padded rows.
 // Shared by the transform kernel and the cost-volume kernel that writes the transformed planes directly: same code, same bits.

@@ -15,7 +15,7 @@ import torch
 from . import arch_spec as spec
 from . import collate
 from .modules import READOUTS
-from .ops import chamfer_distance, disparity_metrics, voxel_iou
+from .ops import chamfer_distance, disparity_metrics, voxel_iou, voxel_surface_points
 
 THRESHOLDS = (0.2, 0.3, 0.4, 0.5)
 
@@ -181,13 +181,24 @@ def test_dataset(model, ds, batch: int = 32, thresholds: Sequence[float] = THRES
     return out
 
 
+def _chamfer_rows(model, l, r, g, first_id: int, cloud_points: int, cloud_seed: int) -> torch.Tensor:
+    """per-sample Chamfer distance of one device batch; (n,D,H,W) ground-truth grids become clouds first, sample i with id first_id + i"""
+    if g.dim() == 4:
+        ids = torch.arange(first_id, first_id + g.shape[0], dtype=torch.int64, device=g.device)
+        g = voxel_surface_points(g.float(), ids, cloud_points, cloud_seed)
+    d1, d2, _, _ = chamfer_distance(model(l, r), g)
+    return d1.mean(1) + d2.mean(1)
+
+
 @torch.no_grad()
 def test_point_net(model, left: torch.Tensor, right: torch.Tensor, gt_clouds: torch.Tensor, batch: int = 32, device="cuda",
-                   group=None) -> Dict[str, object]:
+                   group=None, cloud_points: int = 2048, cloud_seed: int = 0) -> Dict[str, object]:
     """Stereo2Point's metric (the reference's one native op, extensions/chamfer_dist, README.md:59-66): per-sample
     Chamfer distance mean_i min_j |p_i - q_j|^2 + mean_j min_i |p_i - q_j|^2 between the predicted (N,2048,3) cloud and
     the ground-truth (N,M,3) cloud, on the device; with torch.distributed initialised the per-sample scalars of every
-    rank's shard are all-gathered in list order.  (Squared / mean is this build's stated choice — SURVEY.md §8a row 5.)"""
+    rank's shard are all-gathered in list order.  (Squared / mean is this build's stated choice — SURVEY.md §8a row 5.)
+    gt_clouds may also be (N,D,H,W) occupancy grids: each batch's clouds are then drawn on the device (ops.voxel_surface_points,
+    cloud_points points, seed cloud_seed, id = the sample's index in the list), so a validation list's clouds are fixed."""
     import torch.distributed as dist
     dist_on = dist.is_available() and dist.is_initialized()
     world = dist.get_world_size(group) if dist_on else 1
@@ -197,12 +208,42 @@ def test_point_net(model, left: torch.Tensor, right: torch.Tensor, gt_clouds: to
     cd = torch.empty((e0 - b0,), dtype=torch.float32, device=device)
     done = 0
     for l, r, g in _device_batches((left, right, gt_clouds), b0, e0, batch, device):
-        d1, d2, _, _ = chamfer_distance(model(l, r), g)
-        cd[done:done + l.shape[0]] = d1.mean(1) + d2.mean(1)
+        cd[done:done + l.shape[0]] = _chamfer_rows(model, l, r, g, b0 + done, cloud_points, cloud_seed)
         done += l.shape[0]
     if dist_on:
         cd = collate.all_gather_ragged(cd, total, group)
     return {"samples": total, "mean_chamfer": cd.mean().item() if total else float("nan"), "per_sample": cd.cpu()}
+
+
+@torch.no_grad()
+def test_point_dataset(model, ds, batch: int = 32, device="cuda", group=None, workers: int = 0, cloud_points: int = 2048,
+                       cloud_seed: int = 0) -> Dict[str, object]:
+    """test_point_net over a data.StereoShapeNet, as test_dataset is test_net over one: each rank decodes and evaluates its
+    shard_bounds slice, host batches cross PCIe on a copy stream (graph.PrefetchingLoader), the ground-truth clouds are drawn on the
+    device from the tree's occupancy grids (id = the item's index in the list) and the per-sample Chamfer distances are all-gathered in
+    list order; per_taxonomy lists the mean Chamfer distance and sample count per category."""
+    import torch.distributed as dist
+    from . import data as _data
+    from .graph import PrefetchingLoader
+    dist_on = dist.is_available() and dist.is_initialized()
+    world = dist.get_world_size(group) if dist_on else 1
+    rank = dist.get_rank(group) if dist_on else 0
+    total = len(ds)
+    b0, e0 = collate.shard_bounds(total, world, rank)
+    cd = torch.empty((e0 - b0,), dtype=torch.float32, device=device)
+    done = 0
+    for item in PrefetchingLoader(_data.batches(ds, batch, range(b0, e0), workers), device):
+        l, r, g = item[:3]
+        cd[done:done + l.shape[0]] = _chamfer_rows(model, l, r, g, b0 + done, cloud_points, cloud_seed)
+        done += l.shape[0]
+    if dist_on:
+        cd = collate.all_gather_ragged(cd, total, group)
+    cpu = cd.cpu()
+    per_tax: Dict[str, Dict[str, object]] = {}
+    for tax in sorted({it[0] for it in getattr(ds, "items", [])}):
+        idx = [i for i, it in enumerate(ds.items) if it[0] == tax]
+        per_tax[tax] = {"samples": len(idx), "mean_chamfer": cpu[idx].mean().item()}
+    return {"samples": total, "mean_chamfer": cpu.mean().item() if total else float("nan"), "per_sample": cpu, "per_taxonomy": per_tax}
 
 
 @torch.no_grad()

@@ -1106,3 +1106,71 @@ def disparity_epe(pred: torch.Tensor, gt: torch.Tensor):
         _lib.check(_lib.load().s3r_disparity_epe(pred.data_ptr(), gt.data_ptr(), epe.data_ptr(), cnt.data_ptr(), B,
                                                  pred[0].numel(), _stream_ptr(pred.device)), "disparity_epe")
     return epe, cnt
+
+
+def _check_surface(volume, sample_ids, n_points, seed):
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 4:
+        raise RuntimeError("volume must be a (B, D, H, W) fp32 tensor")
+    volume = _check_input(volume, "volume", volume.shape[1:])
+    B = volume.shape[0]
+    if not isinstance(sample_ids, torch.Tensor) or sample_ids.dtype != torch.int64 or tuple(sample_ids.shape) != (B,) \
+            or sample_ids.device != volume.device or not sample_ids.is_contiguous():
+        raise RuntimeError(f"sample_ids must be a contiguous ({B},) int64 tensor on {volume.device}")
+    if int(n_points) < 1:
+        raise ValueError(f"n_points must be positive, got {n_points!r}")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError(f"seed must be in [0, 2^64), got {seed!r}")
+    return volume
+
+
+@torch.no_grad()
+def voxel_surface_points(volume: torch.Tensor, sample_ids: torch.Tensor, n_points: int = 2048, seed: int = 0, threshold: float = 0.5,
+                         return_counts: bool = False, out=None, scratch=None):
+    """(B, n_points, 3) clouds in [-0.5, 0.5]^3 drawn on the exposed faces of the (B, D, H, W) fp32 occupancy grids
+    (`s3r_voxel_surface_points`, include/s3r.h: a sampling rule INVENTED by this build).  sample_ids (B,) int64 ON THE DEVICE: a
+    sample's cloud depends on (seed, its id, its grid, threshold, n_points) only, and an empty grid gives zeros.  return_counts: also
+    the (B,) int32 exposed-face counts.  `out` is (points[, counts]) to write into, `scratch` a float buffer of at least
+    `s3r_voxel_surface_points_scratch_elems` floats.  No autograd: ground truth is data."""
+    volume = _check_surface(volume, sample_ids, n_points, seed)
+    B, D, H, W = volume.shape
+    dev = volume.device
+    if out is None:
+        out = (torch.empty((B, int(n_points), 3), dtype=torch.float32, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev) if return_counts else None)
+    points, counts = out
+    if B:
+        lib = _lib.load()
+        need = lib.s3r_voxel_surface_points_scratch_elems(B, D, H, W)
+        if scratch is None:
+            scratch = _scratch(need, "voxel_surface_points scratch query", dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.s3r_voxel_surface_points(volume.data_ptr(), float(threshold), sample_ids.data_ptr(), int(seed), points.data_ptr(),
+                                                    *_ptrs(counts), B, D, H, W, int(n_points), scratch.data_ptr(), scratch.numel(),
+                                                    _stream_ptr(dev)), "voxel_surface_points")
+    return (points, counts) if return_counts else points
+
+
+class SurfacePoints(nn.Module):
+    """`voxel_surface_points` with its cloud and scratch kept between calls, keyed on the batch's shape: the same addresses at every call,
+    so it can sit inside a captured training step (the graph replays with fresh clouds from the new grids and ids).  `forward` returns
+    the kept tensor: copy what must outlive the next call."""
+
+    def __init__(self, n_points: int = 2048, seed: int = 0, threshold: float = 0.5):
+        super().__init__()
+        self.n_points, self.seed, self.threshold = int(n_points), int(seed), float(threshold)
+        self._key = None
+        self._out = None
+        self._scratch = None
+
+    def forward(self, volume: torch.Tensor, sample_ids: torch.Tensor) -> torch.Tensor:
+        volume = _check_surface(volume, sample_ids, self.n_points, self.seed)
+        key = (tuple(volume.shape), volume.device)
+        if self._key != key:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("SurfacePoints met a new batch shape under stream capture: run one batch of this shape before capturing")
+            B = volume.shape[0]
+            self._out = (torch.empty((B, self.n_points, 3), dtype=torch.float32, device=volume.device), None)
+            self._scratch = _scratch(_lib.load().s3r_voxel_surface_points_scratch_elems(*volume.shape), "SurfacePoints scratch query",
+                                     volume.device) if B else None
+            self._key = key
+        return voxel_surface_points(volume, sample_ids, self.n_points, self.seed, self.threshold, out=self._out, scratch=self._scratch)

@@ -4,8 +4,9 @@ network under autograd (`model.differentiable`), the HIP losses, the HIP optimiz
 
 What a run is a function of: the model's initial state, the data set, `TrainConfig`.  The index order of epoch e is
 `torch.randperm(len(train_set), generator=torch.Generator().manual_seed(seed + e))`; the augmentation of a sample depends on (the
-augmentation's seed, id = e * len(train_set) + index) only; every kernel of the step sums in a fixed order.  Two runs give the same
-per-step losses and parameters bit for bit, and a run resumed from a checkpoint continues with the bits of the uninterrupted one.
+augmentation's seed, id = e * len(train_set) + index) only, and so does the ground-truth cloud that variant "point" draws from a
+sample's occupancy grid (`SurfacePoints`, seed `cloud_seed`, the same id: a fresh cloud of each shape every epoch); every kernel
+of the step sums in a fixed order.  Two runs give the same per-step losses and parameters bit for bit, and a run resumed from a checkpoint continues with the bits of the uninterrupted one.
 Nothing is read back from the device inside an epoch: the per-step losses stay on the device until the epoch ends.
 
 The step runs eagerly.  Single GPU, fp32 models only: there is no gradient all-reduce and no bf16 backward.
@@ -24,7 +25,7 @@ from . import checkpoint, evaluate
 from . import optim as _optim
 from .augment import AugmentConfig, StereoAugment
 from .graph import PrefetchingLoader
-from .ops import ChamferDistance, DisparityLoss, VoxelBCELoss
+from .ops import ChamferDistance, DisparityLoss, SurfacePoints, VoxelBCELoss
 
 __all__ = ["TrainConfig", "fit", "loss_of_batch", "learning_rate", "epoch_order"]
 
@@ -52,6 +53,8 @@ class TrainConfig:
     seed: int = 0
     workers: int = 0
     max_steps: Optional[int] = None              # stop (and save) once this many steps have run in total
+    cloud_points: int = 2048                     # variant "point" on (D,H,W) grids: points per ground-truth cloud ...
+    cloud_seed: int = 0                          # ... and the seed of ops.voxel_surface_points
 
     def __post_init__(self):
         if self.variant not in ("voxel", "point"):
@@ -128,7 +131,8 @@ def validate(model, val_set, cfg: TrainConfig, device) -> dict:
                for i in range(0, left.shape[0], cfg.batch)]
         left, right = torch.cat([o[0] for o in out]).cpu(), torch.cat([o[1] for o in out]).cpu()
     if cfg.variant == "point":
-        res = evaluate.test_point_net(model, left, right, target, batch=cfg.batch, device=device)
+        res = evaluate.test_point_net(model, left, right, target, batch=cfg.batch, device=device, cloud_points=cfg.cloud_points,
+                                      cloud_seed=cfg.cloud_seed)
         return {"samples": res["samples"], "mean_chamfer": res["mean_chamfer"], "score": -res["mean_chamfer"]}
     res = evaluate.test_net(model, left, right, target, batch=cfg.batch, device=device)
     return {"samples": res["samples"], "thresholds": res["thresholds"], "mean_iou": res["mean_iou"], "score": max(res["mean_iou"])}
@@ -136,7 +140,8 @@ def validate(model, val_set, cfg: TrainConfig, device) -> dict:
 
 def fit(model, train_set, val_set, cfg: TrainConfig, log: Optional[Callable[[dict], None]] = None) -> dict:
     """Train `model` (a Stereo2Voxel or Stereo2Point on the GPU, fp32) on `train_set`, a map-style data set whose items are
-    (left, right, target[, disp_left, disp_right]): uint8 renders (3 or 4, H, W), target the (32,32,32) occupancy or the (M,3) cloud.
+    (left, right, target[, disp_left, disp_right]): uint8 renders (3 or 4, H, W), target the (32,32,32) occupancy or the (M,3) cloud
+    (variant "point" also takes the occupancy grid and draws `cloud_points` points on its surface on the device, every step).
     `val_set` is such a set, a tuple of stacked tensors, or None.  Returns {"losses": the per-step losses of THIS call as floats,
     "epochs": one record per finished epoch (what `log` received), "step", "epoch", "best", "optimizer", "checkpoint"}."""
     if getattr(model, "precision", "fp32") != "fp32":
@@ -156,6 +161,7 @@ def fit(model, train_set, val_set, cfg: TrainConfig, log: Optional[Callable[[dic
         opt.load_state_dict(ck["optimizer"])
         epoch, step, best = ck["epoch"], ck["step"], ck["best"]
     aug = StereoAugment(cfg.augment or AugmentConfig.identity())
+    clouds = SurfacePoints(cfg.cloud_points, cfg.cloud_seed)
     losses_fn = (VoxelBCELoss() if cfg.variant == "voxel" else ChamferDistance(), DisparityLoss())
     per_epoch = -(-n // cfg.batch)
     losses, records, last_path = [], [], None
@@ -183,6 +189,8 @@ def fit(model, train_set, val_set, cfg: TrainConfig, log: Optional[Callable[[dic
             with_disp = len(fields) >= 6
             out = aug(fields[0], fields[1], ids, *(fields[3:5] if with_disp else ()))
             target = fields[2].float()
+            if cfg.variant == "point" and target.dim() == 4:
+                target = clouds(target, ids)
             opt.zero_grad(set_to_none=True)
             loss = loss_of_batch(model, cfg, out[0], out[1], target, *(out[2:4] if with_disp else ()), losses=losses_fn)
             loss.backward()
