@@ -1,12 +1,14 @@
 // Host-side internals shared by the host translation units of libs3r_hip.so — s3r_prof.hip (event profiler), s3r_plan.hip (layer
-// geometry, kernel policy, sizes, the packed weight image's layout, chain / arena planner) and s3r_api.hip (one runner per kernel
-// path, the dispatcher over them and the C-ABI entry points).  Not part of the ABI (include/s3r.h) and not seen by the kernel
-// sources (those share s3r_kernels.h).
+// geometry, kernel policy, sizes, the packed weight image's layout, chain / arena planner), s3r_conv_forward.hip (one runner per
+// kernel path, the dispatcher over them and their entry points) and s3r_api_layers.hip / s3r_api_tasks.hip (the other C-ABI entry
+// points, by family); last, the argument checks those entry points share.  Not part of the ABI (include/s3r.h) and not seen by the
+// kernel sources (those share s3r_kernels.h).
 #pragma once
 #include "../../include/s3r.h"
 #include "s3r_kernels.h"
 
 #include <cstdint>
+#include <initializer_list>
 #include <vector>
 
 namespace s3rh {
@@ -165,5 +167,65 @@ s3r::ConvParams make_params(const s3r_conv_desc* d, const Geo& g);
 int resolve_launch(const s3r_conv_desc* d, s3r::ConvParams* p, Launch* L);
 int64_t align_up(int64_t v, int64_t a);
 int plan_chain(const s3r_layer* layers, int n, Plan* pl);
+
+// ---------------------------------------------------------------- argument checks shared by the entry points
+// Each states one rule of include/s3r.h once; all run on the host, before anything is enqueued.  A check returns S3R_OK or fail(...).
+inline int null_tensor() { return fail(S3R_ERR_INVALID, "null tensor pointer"); }
+// bf16 tensors (channels-last activations, and the scratch / workspace that holds them) are read and written with 16-byte accesses
+// whose addresses are base + a multiple of 16 bytes: the base must be 16-byte aligned (include/s3r.h, Conventions).  fp32 and int32
+// tensors need their natural 4 bytes only
+inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+inline int bf16_align_fail(const char* what, const void* p) {
+    return fail(S3R_ERR_INVALID, "%s must be 16-byte aligned (got %p): bf16 tensors are accessed 16 bytes at a time", what, p);
+}
+// the stems fetch render rows by 16-byte vector loads / LDS-DMA from base + row * width (fp32 and 8-bit renders alike)
+inline int check_renders_aligned(const void* left, const void* right) {
+    if (!misaligned16(left) && !misaligned16(right)) return S3R_OK;
+    return fail(S3R_ERR_INVALID, "render tensors must be 16-byte aligned (got %p, %p)", left, right);
+}
+// scratch NULL or smaller than the need; `who`: the entry's words in front of "needs", `query`: the size query to name
+inline int need_scratch(int code, const char* who, int64_t need, const char* query, const void* scratch, int64_t scratch_elems) {
+    if (scratch && scratch_elems >= need) return S3R_OK;
+    return fail(code, "%s needs %lld floats of scratch (%s), got %lld", who, (long long)need, query, (long long)(scratch ? scratch_elems : 0));
+}
+// the end of an entry point: what its launch answered
+inline int launched(hipError_t e, const char* what) { return e == hipSuccess ? S3R_OK : hip_fail(e, what); }
+// the epilogues of the backward kernels know none / ReLU / sigmoid, and read y only where the activation's derivative needs it
+inline int check_act(int act, const char* who) {
+    if (act >= S3R_ACT_NONE && act <= S3R_ACT_SIGMOID) return S3R_OK;
+    return fail(S3R_ERR_INVALID, "%s takes none / relu / sigmoid (act %d)", who, act);
+}
+inline int check_y(int act, const void* y, const char* who) {
+    if (act == S3R_ACT_NONE || y) return S3R_OK;
+    return fail(S3R_ERR_INVALID, "%s: y is NULL (it may be only when act is none)", who);
+}
+// The header's limits on one tensor (< 2^31 elements, < 4 GiB): true when the product of the first 1, 2, ... extents has 2^31 elements
+// or more, or the whole tensor 4 GiB or more at `elem_bytes` bytes an element (1: the element limit is the tighter one).  Factor by
+// factor, so no int64 product overflows whatever the extents.  An extent of 0 (an empty batch) makes every later product 0: list it
+// FIRST where an empty call is never too large, LAST where its per-sample extents are still checked
+inline bool too_large(std::initializer_list<int64_t> extents, int elem_bytes) {
+    int64_t n = 1;
+    for (int64_t e : extents) {
+        if (e > 0 && n > (kMaxElems - 1) / e) return true;
+        n *= e;
+    }
+    return elem_bytes * n >= kMaxBytes;
+}
+inline int too_large_fail() { return fail(S3R_ERR_INVALID, "tensor of 4 GiB or more: split the batch"); }
+// tensors of a call that must not share memory (NULL: absent): byte spans, and the outputs against each other and the inputs
+struct Span { const void* p; int64_t bytes; const char* name; };
+inline bool overlap(const Span& a, const Span& b) {
+    const uintptr_t x = (uintptr_t)a.p, y = (uintptr_t)b.p;
+    return a.p && b.p && x < y + (uintptr_t)b.bytes && y < x + (uintptr_t)a.bytes;
+}
+inline int check_overlaps(const char* who, const Span* outs, int n_outs, const Span* ins, int n_ins) {
+    for (int i = 0; i < n_outs; ++i) {
+        for (int j = i + 1; j < n_outs; ++j)
+            if (overlap(outs[i], outs[j])) return fail(S3R_ERR_INVALID, "%s: %s and %s overlap", who, outs[i].name, outs[j].name);
+        for (int j = 0; j < n_ins; ++j)
+            if (overlap(outs[i], ins[j])) return fail(S3R_ERR_INVALID, "%s: %s overlaps the input %s", who, outs[i].name, ins[j].name);
+    }
+    return S3R_OK;
+}
 
 }  // namespace s3rh

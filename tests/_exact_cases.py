@@ -525,7 +525,7 @@ def tile1_batch(n_out):
 
 
 def _head_chains():
-    """the fp32 conv + head launch (s3r_api.hip: conv_head_fused, which rides on run_dwino / run_dwino3 or launches the direct kernel
+    """the fp32 conv + head launch (s3r_conv_forward.hip: conv_head_fused, which rides on run_dwino / run_dwino3 or launches the direct kernel
     itself), one row per route, each under the head's four epilogue forms and
     the producer forms null and int.  The head has bn=True so that head_scale is a real vector, and act none: negative sums count.
     (Its one channel draws its scale from four values: seed 997 gives scale 2, a non-zero shift and non-zero weights on the first and the

@@ -1,0 +1,61 @@
+"""tests/golden/abi_refusals.json: for every C-ABI entry point behind the forward dispatcher, the return code and the
+s3r_last_error() text of each refused call of tests/_refusal_cases.py — every check alone, adjacent checks together (their order),
+scratch missing and one float short, an empty batch, the scratch queries.  Compared EXACTLY: the file was written
+(tests/golden/make_abi_refusals_golden.py) by the build before the entry points were split by family, and holds results only.
+
+The calls are made once, in a child process that sees no device (a case that stopped refusing finds nothing to launch on)."""
+import json
+import os
+
+import pytest
+
+from tests import _refusal_cases as RC
+
+CSRC = os.path.join(RC.ROOT, "stereo-3d-reconstruction_amd", "csrc")
+
+
+@pytest.fixture(scope="module")
+def golden(golden_dir):
+    doc = json.load(open(os.path.join(golden_dir, "abi_refusals.json")))
+    assert doc["generated_at_commit"] not in ("", "unknown")
+    return doc["cases"]
+
+
+@pytest.fixture(scope="module")
+def answers():
+    return RC.run_in_child()
+
+
+def test_the_golden_covers_every_entry_point_and_holds_refusals_only(s3r, golden):
+    assert sorted(golden) == sorted(RC.CASE_IDS)
+    block = set(s3r._lib.SIGNATURES) - {"s3r_abi_version", "s3r_last_error", "s3r_conv_out_size", "s3r_conv_packed_elems", "s3r_conv_scratch_elems",
+                                        "s3r_chain_workspace_elems", "s3r_conv_wino_input_elems", "s3r_conv_wino_input_layout",
+                                        "s3r_profile_enable", "s3r_profile_reset", "s3r_profile_detail", "s3r_profile_read"}
+    assert {row.entry for row in RC.ROWS} == block      # (the others: the version, the message, s3r_plan.hip's queries, the profiler)
+    for cid, (rc, text) in golden.items():
+        assert rc != RC.ERR_HIP, (cid, text)               # a launch was reached
+        assert (rc < 0) == (text is not None), cid
+        if rc >= 0:      # an empty batch, or an entry that enqueues nothing (a query's size, s3r_conv_adjoint_desc)
+            row = next(r for r in RC.ROWS if r.entry == cid.split(":")[0])
+            assert ":empty-" in cid or cid.endswith(":shape-empty-large") or not row.launches, cid
+    for row in RC.ROWS:      # a refusal for want of scratch states the need and the query
+        if row.scratch:
+            for kind in ("scratch-null", "scratch-short"):
+                rc, text = golden[f"{row.entry}:{kind}"]
+                assert rc in (-1, -3) and ("scratch" in text or "workspace" in text), (row.entry, rc, text)
+
+
+@pytest.mark.parametrize("cid", RC.CASE_IDS)
+def test_refusal(golden, answers, cid):
+    assert answers[cid] == golden[cid]
+
+
+def test_every_fail_site_of_the_entry_point_sources_is_reached_or_listed(golden):
+    texts = [text for _, text in golden.values() if text is not None]
+    formats = [f for name in RC.ENTRY_SOURCES for f in RC.fail_formats(open(os.path.join(CSRC, name)).read())]
+    assert len(formats) >= 60
+    assert set(RC.UNREACHABLE) <= set(formats), "a listed site is gone from the sources"
+    missing = [f for f in formats if f not in RC.UNREACHABLE and not any(RC.format_pattern(f).fullmatch(t) for t in texts)]
+    assert not missing, missing
+    for f in RC.UNREACHABLE:
+        assert not any(RC.format_pattern(f).fullmatch(t) for t in texts), f"listed as unreachable but reached: {f}"
