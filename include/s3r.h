@@ -170,7 +170,7 @@ typedef enum s3r_layout { S3R_LAYOUT_PLAIN = 0, S3R_LAYOUT_WINO_H = 2, S3R_LAYOU
 
 /* Which convolution algorithm a layer's forward runs (ABI 7).  The fp32 3 x 3 [x 3] stride-1 pad-1 convolutions and the
  * transposed convolutions have two kernels — the direct implicit GEMM and a Winograd form with 1/2 .. 9/16 of the
- * multiplications (csrc/s3r_conv_wino.hip) — that agree to fp32 rounding, NOT bit for bit.  So the choice is part of the
+ * multiplications (csrc/s3r_wino.h and its units) — that agree to fp32 rounding, NOT bit for bit.  So the choice is part of the
  * descriptor and never depends on anything else a caller passes (workspace size, batch):
  *   S3R_ALGO_AUTO      the library's policy, a function of the layer's PER-SAMPLE geometry only: Winograd where the layer has
  *                      that form (fp32 Conv k3 s1 p1 with cin % 32 == 0, cout > 1, edge >= 4; ConvTranspose3d k4 s2 p1 over an
@@ -266,7 +266,7 @@ const char* s3r_last_error(void);
 int s3r_conv_out_size(const s3r_conv_desc* d);
 /* size of the packed weight buffer for a layer IN 4-BYTE UNITS (>= the torch weight's numel on the fp32
  * path: couts are padded; about half of it on the bf16 path).  An fp32 3 x 3 [x 3] stride-1 pad-1 convolution packs every
- * form it has: the direct slab, the six Winograd F(4,3)-along-H class slabs (csrc/s3r_conv_wino.hip: half the
+ * form it has: the direct slab, the six Winograd F(4,3)-along-H class slabs (csrc/s3r_wino_axis1.hip: half the
  * multiplications) and the 36 slabs of the two-axis form (2D over H, W; 3D over D, H; a 3D k4 valid layer its 25); which kernel a forward
  * runs is the descriptor's `algo` (s3r_algo above).  The transposed convolutions likewise: 72 F(2,2) x F(2,2) (parity class, class) slabs
  * behind the direct ones. */

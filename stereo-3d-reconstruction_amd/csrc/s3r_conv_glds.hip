@@ -789,7 +789,7 @@ static hipError_t launch_cfg(ConvParams p, hipStream_t stream) {
         hipLaunchKernelGGL((conv_glds_kernel<WM, WN, TM, TN, VEC, HEAD, NBUF>), grid, dim3(256), lds, stream, p);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess && p.ksplit > 1) {
-            if (p.out_mode) {      // the finish pass writes the consumer's plane sets (s3r_conv_wino.hip): in place of conv_finish_kernel
+            if (p.out_mode) {      // the finish pass writes the consumer's plane sets (s3r_wino_handoff.hip): in place of conv_finish_kernel
                 g_launch_count += 1;
                 e = launch_wino_handoff(p, 3, p.out_mode - 1, p.n_tiles * BN, stream);
             } else e = launch_conv_finish(p, p.n_tiles * BN, stream);

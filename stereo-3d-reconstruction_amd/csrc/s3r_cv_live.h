@@ -1,5 +1,5 @@
 /* Which K tiles of v1's class GEMM read nothing but the cost volume's structural zeros: the ONE statement of the rule, shared by the
- * class kernel (s3r_conv_wino.hip, wino_body<.., CVL>) and by the host test that checks it against a volume rebuilt in numpy
+ * class kernel (s3r_wino_gemm.hip, wino_body<.., CVL>) and by the host test that checks it against a volume rebuilt in numpy
  * (tests/test_cv_live_cpu.py compiles this header as plain C).
  *
  * The cost volume of edge n (D = H = W = n, n % 4 == 0) is masked by construction (s3r_pointwise.hip, cost_volume_wino2_kernel):

@@ -1,7 +1,7 @@
 // ConvTranspose3d(k4 s2 p1), fp32, Winograd F(2,2) on ALL THREE axes inside every output-parity class: 27 products for 2 x 2 x 2
-// outputs where the two-axis form of s3r_conv_wino.hip spends 36 and the direct form 64 (27 / 64 = 0.42 of the multiplications).
+// outputs where the two-axis form of s3r_wino_gemm.hip spends 36 and the direct form 64 (27 / 64 = 0.42 of the multiplications).
 //
-// Along one axis (s3r_conv_wino.hip, section 2): outputs 2q and 2q + 1 of parity r read the padded inputs X0, X1, X2 = x[2q + r ..
+// Along one axis (s3r_wino_axis1.hip, the transposed forms): outputs 2q and 2q + 1 of parity r read the padded inputs X0, X1, X2 = x[2q + r ..
 // 2q + r + 2] through the parity's two taps g0, g1:   m0 = (X0 - X1) g0,  m1 = X1 (g0 + g1),  m2 = (X1 - X2) g1,
 // y(2q) = m0 + m1,  y(2q + 1) = m1 - m2.  Nested over D, H, W that is 27 classes (a, b, c), each a 1 x 1 x 1 convolution (K = Cin)
 // of its own input combination with its own weight sum.

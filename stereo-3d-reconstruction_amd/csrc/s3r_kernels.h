@@ -127,7 +127,7 @@ struct ConvParams {
     const float* head_scale;   // [1] or null
     const float* head_shift;   // [1] or null
     int head_act;
-    // Winograd along H (s3r_conv_wino.hip): x = the transformed input plane sets, x_cls elements apart; Nh = row groups per
+    // Winograd along H (s3r_wino_gemm.hip): x = the transformed input plane sets, x_cls elements apart; Nh = row groups per
     // plane; Hout = the output's true height.  Two-axis form (D and H): Nd = depth groups, Dout = the true depth, ncls = the
     // number of (depth class, row class) plane sets / weight slabs (0: the one-axis form's own count)
     int x_cls, Hout, Dout, ncls;
@@ -135,7 +135,7 @@ struct ConvParams {
     // depth differences Dd and the mixed differences Ddh (materialised), 0: those are formed inside the class kernel
     const float* xd;
     int xd_mode;
-    // hand-off (s3r_conv_wino.hip, launch_wino_handoff): 0 the layer's own finish pass writes the plain output; 1 + cons: ONE pass
+    // hand-off (s3r_wino_handoff.hip, launch_wino_handoff): 0 the layer's own finish pass writes the plain output; 1 + cons: ONE pass
     // finishes the raw sums in `part` and writes the CONSUMER's operand to y — cons 0 / 1 the two-axis plane sets of a Conv3d k3 p1 /
     // k4 p0, 2 [x | Dh | Dd | Ddh] of a transposed Winograd layer; y_hs / y_ds / y_cs / y_org still describe the halo-padded plain
     // output, which is the consumer's input geometry
@@ -158,7 +158,7 @@ constexpr int kTClsMax = 27;                 // stride 3 in 3D; more classes (st
 struct TClsTable { int n; TClsEntry e[kTClsMax]; };
 hipError_t launch_conv_tcls(const ConvParams& base, TClsTable tab, hipStream_t stream);     // fills wg_begin; base.w = the first slab
 
-// Launch form of a Winograd layer (s3r_conv_wino.hip): serial (one workgroup walks all classes of its tile), class-parallel (one
+// Launch form of a Winograd layer (s3r_wino_gemm.hip): serial (one workgroup walks all classes of its tile), class-parallel (one
 // workgroup per (tile, class), class sums to slabs, a finish kernel transforms them — bit-identical to the serial form), or dual
 // (positions [0, n_cut) serial and [n_cut, N) class-parallel in one launch).
 enum { WINO_SERIAL = 0, WINO_CP = 1, WINO_DUAL = 2 };
@@ -207,7 +207,7 @@ int conv_num_tiles();
 void conv_tile_dims(int tile_cfg, int* bm, int* bn);
 hipError_t launch_pack_conv(const float* w, float* wp, int Cin, int Cout, int CoutPad, int T, int transposed,
                             hipStream_t s);
-// Winograd F(2,3) along H for 3 x 3 [x 3] stride-1 pad-1 convolutions (s3r_conv_wino.hip)
+// Winograd F(2,3) along H for 3 x 3 [x 3] stride-1 pad-1 convolutions (s3r_wino_axis1.hip, s3r_wino_gemm.hip)
 hipError_t launch_wino_input(const float* x, float* V, long long planes, int Hp, int Wp, int Hq, int R, hipStream_t s);
 hipError_t launch_pack_wino(const float* w, float* wp, int Cin, int Cout, int CoutPad, int kd, int kw, int R, hipStream_t s);
 // kind: 1 conv F(4,3), 2 transposed F(2,2) x F(2,2); kcls = K per class (Cin x taps per class); ntotal = positions (groups of R output
@@ -416,7 +416,7 @@ hipError_t launch_surface_points(const float* occ, float threshold, const int64_
                                  int B, int D, int H, int W, int n_points, float* scratch, hipStream_t s);
 
 #if defined(__HIPCC__)
-// Winograd F(4, 3) input transform along one axis (s3r_conv_wino.hip): the six class values of six consecutive padded rows.
+// Winograd F(4, 3) input transform along one axis (s3r_wino_axis1.hip; wax_bt, s3r_wino.h): the six class values of six consecutive padded rows.
 // Shared by the transform kernel and the cost-volume kernel that writes the transformed planes directly: same code, same bits.
 template <int R>
 __device__ __forceinline__ void wino_rows_to_classes(const float (&r)[R + 2], float (&v)[R + 2]) {

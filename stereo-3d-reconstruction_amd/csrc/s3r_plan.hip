@@ -320,7 +320,7 @@ int check_halos(const s3r_conv_desc* d, Route r) {
 
 int cout_pad(int cout) { return (cout + 127) / 128 * 128; }
 
-// Winograd along H (s3r_conv_wino.hip) for the fp32 3 x 3 [x 3] stride-1 pad-1 convolutions (F(4,3): 1/2 of the matrix work, F(2,3):
+// Winograd along H (s3r_wino_axis1.hip, s3r_wino_gemm.hip) for the fp32 3 x 3 [x 3] stride-1 pad-1 convolutions (F(4,3): 1/2 of the matrix work, F(2,3):
 // 2/3) and the transposed convolutions (F(2,2) along D and H inside the parity classes: 9/16): another summation order than the direct
 // kernels' — same fp32 accuracy, other bits.  Such a layer's packed weights hold BOTH forms (the direct slab, then the class
 // slabs); which kernel a call runs is the descriptor's `algo` (include/s3r.h): AUTO resolves from the layer's per-sample
@@ -367,7 +367,7 @@ bool wino_desc_ok(const s3r_conv_desc* d) {
     return d->in_layout == S3R_LAYOUT_PLAIN || (d->in_layout == S3R_LAYOUT_WINO_H && wino_layer(d)) ||
            (d->in_layout == S3R_LAYOUT_DIFF && dwino_layer(d));
 }
-// Two-axis class-parallel Winograd (s3r_conv_wino.hip): the stride-1 layers with a small edge — Conv3d k3 p1 as F(4,3) x F(4,3)
+// Two-axis class-parallel Winograd (s3r_wino_axis2.hip): the stride-1 layers with a small edge — Conv3d k3 p1 as F(4,3) x F(4,3)
 // over D and H (returns 0), Conv3d k4 p0 as F(2,4) x F(2,4) (returns 1), Conv2d k3 p1 as F(4,3) x F(4,3) over H and W (returns 2);
 // -1: the layer has no such form
 int wino2_ax(const s3r_conv_desc* d) {
@@ -379,7 +379,7 @@ int wino2_ax(const s3r_conv_desc* d) {
     if (d->k == 4 && d->pad == 0 && d->in_size >= 5) return 1;
     return -1;
 }
-// The LDS rule of the two-axis finish kernels (s3r_conv_wino.hip, launch_conv_wino2: it keeps its own checks).  Both stage PADDED
+// The LDS rule of the two-axis finish kernels (s3r_wino_axis2.hip, launch_conv_wino2: it keeps its own checks).  Both stage PADDED
 // output planes in 64 KiB: the Conv2d finish one plane, (out + 2 out_halo)^2 floats, hence a padded edge <= 128 (a layer writing
 // its consumer's plane sets stages the halo-1 plane: always inside, the edge stops at 124); the semi-fused Conv3d finish four
 // slices, hence a padded edge <= 64.  The class-parallel Conv3d form stages nothing.  Part of the PLAN: a descriptor outside the
@@ -557,7 +557,7 @@ PackedLayout packed_layout(const s3r_conv_desc* d, const Geo& g) {
 }
 // The depth differences of the transposed Winograd form are materialised (two more tensors behind the row differences) while
 // the four tensors stay in the Infinity Cache, and formed inside the class kernel otherwise: same bits either way, so this
-// may follow the batch (s3r_conv_wino.hip).
+// may follow the batch (s3r_wino_gemm.hip).
 bool dwino_materialise(const s3r_conv_desc* d) {
     static const int forced = getenv("S3R_DWINO_MAT") ? atoi(getenv("S3R_DWINO_MAT")) : -1;      // A/B switch, read once
     if (forced >= 0) return forced != 0;
@@ -867,7 +867,7 @@ static int handoff_mask() {
     return m == 1 ? ~0 : m;
 }
 
-// 3D hand-off of the pair (a, b) — a's finish pass writing b's operand (s3r_conv_wino.hip, wino_handoff_kernel).  Returns the layout
+// 3D hand-off of the pair (a, b) — a's finish pass writing b's operand (s3r_wino_handoff.hip, wino_handoff_kernel).  Returns the layout
 // the pair's ALGORITHMS allow (PLAIN: none) — a function of the descriptors alone, which sizes the region — and through *take
 // whether the launch forms planned for this batch on this device take it (both routes give the same bits, so that may follow the
 // batch): the producer must leave whole-range raw sums in slabs (split-K; class-parallel), the consumer's operand must fit one call

@@ -301,7 +301,7 @@ __global__ __launch_bounds__(256) void cost_volume_kernel(const float* __restric
     }
 }
 
-// The cost volume written straight into the layout its consumer's Winograd kernel reads (s3r_conv_wino.hip, S3R_LAYOUT_WINO_H):
+// The cost volume written straight into the layout its consumer's Winograd kernel reads (s3r_wino_axis1.hip, S3R_LAYOUT_WINO_H):
 // V_i[b][ch][1 + d][q][wp], i = 0 .. R+1, from the padded rows R q .. R q + R + 1 of plane d of the halo-1 volume through
 // wino_rows_to_classes (the very function wino_input_kernel applies to the padded volume: bit-identical) — the volume itself (221 MB at B = 32) is never written
 // or re-read.  One workgroup per (b, c) as above; per class and slab the planes d = 0 .. D-1 are one contiguous run.
@@ -362,7 +362,7 @@ hipError_t launch_cost_volume_wino(const float* fl, const float* fr, float* V, i
     return hipGetLastError();
 }
 
-// ... and as the 36 TWO-AXIS plane sets (F(4,3) along D and H: s3r_conv_wino.hip, wino2_input_kernel, S3R_LAYOUT_WINO_DH):
+// ... and as the 36 TWO-AXIS plane sets (F(4,3) along D and H: s3r_wino_axis2.hip, wino2_input_kernel, S3R_LAYOUT_WINO_DH):
 // V[6 a + b][bb][ch][sd][wp][sh] — the column OUTSIDE the row group, so that 64 consecutive positions of the consumer's class GEMM
 // are whole columns of every row group and the volume's masked triangle forms whole K tiles it can leave out (s3r_cv_live.h) —
 // from the 6 x 6 window of padded depths 4 sd .. 4 sd + 5 and padded rows 4 sh .. 4 sh + 5 at column

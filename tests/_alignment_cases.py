@@ -19,7 +19,7 @@ the fp32-typed scratch / ws of a bf16 call 4 and 36 floats; an argument of the e
 launches a kernel on a bf16 or 8-bit tensor that is less than 16-byte aligned: those are refusals (tests/test_abi_cpu.py, and the
 stem cases here, which assert the refusal on the device before the call proper).
 
-Which case takes which side of the four address-dependent branches of s3r_conv_wino.hip:
+Which case takes which side of the four address-dependent branches of the Winograd units (s3r_wino_*.hip):
 
   launch_wino_diff (the two-column kernel iff x and the difference scratch are 8-byte aligned and Wp is even; the scalar
       wino_diff_kernel otherwise): dwino-tile0-d2, dwino-tile1-d1, dwino-tile2-d2, wino3-tile6/7/8-deconv3d-64to32-e8 (Wp = n + 2 is

@@ -19,7 +19,7 @@ LeakyReLU with a power-of-two slope (1/4 and 1/2: fused in the kernels' epilogue
 and Tanh evaluate transcendental functions and cannot be exact: they stay with tests/_ref64.py's bound; `exact_act` substitutes
 an exact activation in the cases taken from tests/_buffer_cases.py.
 
-Winograd forms.  The kernels fold G into the packed weights in fp32 (s3r_conv_wino.hip: pack_wino_kernel and wax_g, constants
+Winograd forms.  The kernels fold G into the packed weights in fp32 (s3r_wino_axis1.hip: pack_wino_kernel, and s3r_wino.h: wax_g, constants
 1/4, 1/6, 1/12, 1/24 for F(4, 3) and 1/2, 1/6, 1/3, 2/3, 4/3 for F(2, 4) with the points 0, +-1, 2, inf; the F(2, 2) classes of a
 transposed layer use sums of taps only).  Per transformed axis the lattice step is the lcm of G's denominators, from
 tools/wino_matrices.py's construction in exact arithmetic: F(4, 3) 24, F(2, 4) 6, F(2, 2) 1 (`wino_step`).  B^T and A^T are

@@ -1,6 +1,6 @@
 """Kernel mutants: subtly wrong copies of the HIP kernels that the GPU suite must fail on.  Plain data.
 
-Each entry: `id`; `file` under csrc/ (a translation unit of the Makefile's SRCS, or s3r_ordered.h, which rebuilds its users);
+Each entry: `id`; `file` under csrc/ (a translation unit of the Makefile's SRCS, or a header, which rebuilds its users);
 `anchor`, a span of that file's text that occurs exactly once; `replacement` for it; `kills`, pytest arguments (node ids, at most
 one `-k` expression) naming the tests meant to catch the defect, the likeliest first (the child stops at the first failure);
 `models`, one sentence on the defect.  An entry with `equivalent` (a written argument) changes no observable bit: it still runs
@@ -40,29 +40,29 @@ MUTANTS = [
          kills=["tests/test_general_gpu.py::test_rgb_first_layers_are_unfolded_and_leaky_relu_is_fused",
                 EX + "::test_direct_fp32[leaky-half-fused-epilogue]"],
          models="The fused LeakyReLU of the direct epilogue is a plain ReLU."),
-    # ---- s3r_conv_wino.hip
-    dict(id="wino_bt_coefficient", file="s3r_conv_wino.hip",
+    # ---- s3r_wino.h and its units (s3r_wino_axis1 / _axis2 / _handoff.hip)
+    dict(id="wino_bt_coefficient", file="s3r_wino_axis1.hip",
          anchor="        wino_rows_to_classes<R>(r, v);\n",
          replacement="        wino_rows_to_classes<R>(r, v);\n        v[3] = fmaf(3.f, r[3] - r[1], r[4] - r[2]);\n",
          kills=[EX + "::test_winograd_fp32", "-k", "wino1-serial"],
          models="One coefficient of the F(4,3) input transform (wino_rows_to_classes<4>, class 3: 2 -> 3) in the one-axis "
                 "transform kernel."),
-    dict(id="wino_at_coefficient", file="s3r_conv_wino.hip",
+    dict(id="wino_at_coefficient", file="s3r_wino.h",
          anchor="y[3] = fmaf(8.f, d34, d12) + m[5];",
          replacement="y[3] = fmaf(6.f, d34, d12) + m[5];",
          kills=[EX + "::test_winograd_fp32", "-k", "wino1-class-parallel or wino1-serial"],
          models="One coefficient of the F(4,3) output transform that wino_finish_kernel and the serial form share (8 -> 6)."),
-    dict(id="wino_f24_coefficient", file="s3r_conv_wino.hip",
+    dict(id="wino_f24_coefficient", file="s3r_wino.h",
          anchor="y[1] = fmaf(2.f, m[3], m[1] - m[2]) + m[4];",
          replacement="y[1] = fmaf(3.f, m[3], m[1] - m[2]) + m[4];",
          kills=[EX + "::test_winograd_fp32", "-k", "v6"],
          models="One coefficient of the F(2,4) output transform (2 -> 3)."),
-    dict(id="wino2s_finish_drops_class", file="s3r_conv_wino.hip",
+    dict(id="wino2s_finish_drops_class", file="s3r_wino_axis2.hip",
          anchor="for (int a = 0; a < N; ++a) m[a] = src[(a * M + v) * 64];",
          replacement="for (int a = 0; a < N; ++a) m[a] = a == N - 1 ? 0.f : src[(a * M + v) * 64];",
          kills=[EX + "::test_winograd_fp32", "-k", "wino2-tile and (v1 or v3 or v5)"],
          models="The semi-fused two-axis finish (wino2s_finish_kernel) drops its last depth class; the class-parallel form stays right."),
-    dict(id="wino_handoff_neighbour_class", file="s3r_conv_wino.hip",
+    dict(id="wino_handoff_neighbour_class", file="s3r_wino_handoff.hip",
          anchor="p.y[(size_t)(a * N + c) * total + base + t] = v[a];",
          replacement="p.y[(size_t)(a * N + c) * total + base + t] = v[(a == 2 && c == 3) ? 1 : a];",
          kills=["tests/test_handoff3d_gpu.py::test_pair_equals_the_two_layers_run_singly"],

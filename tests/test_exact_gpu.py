@@ -45,7 +45,7 @@ with the NaN fill of the output and the scratch intact, and the library's own la
 three tests beside the sweep (the planner half is tests/test_exact_cpu.py::test_two_axis_lds_rule_is_the_planners).
 
 Staying on tests/_ref64.py's bound (tests/test_buffers_gpu.py's chain matrix): the e6 -> e7 two-axis hand-off AS A CHAIN.  The
-producer's weights must be multiples of 576 (wax_g in s3r_conv_wino.hip folds 1/24 per axis into them), so the intermediate is
+producer's weights must be multiples of 576 (wax_g in s3r_wino.h folds 1/24 per axis into them), so the intermediate is
 a multiple of 576, and the consumer's weights bring another 576: one unit product is 3.3e5 and the flow passes 2^24 after a few
 dozen terms, whatever the data.  e6 and e7 are held exactly one at a time (wino2-tile3/4/5-e6, -e7).  The activations Sigmoid, ELU
 and Tanh stay there too (transcendental), and the 8-bit stem entry (it scales by 1/255; it is tied to the fp32 entry bit for bit).
@@ -250,7 +250,7 @@ def test_epilogue_forms(s3r, lib, case, monkeypatch):
 
 
 def _semi_fused_batch(l, n):
-    """smallest batch at which the library takes the semi-fused form of a two-axis Conv3d on this device (s3r_conv_wino.hip,
+    """smallest batch at which the library takes the semi-fused form of a two-axis Conv3d on this device (s3r_wino_axis2.hip,
     wino2_form: six workgroups per 64-cout x 64-position tile fill the compute units' four slots twice over)"""
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     B = 1

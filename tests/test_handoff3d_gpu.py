@@ -1,4 +1,4 @@
-"""The 3D hand-off passes (csrc/s3r_conv_wino.hip, wino_handoff_kernel): a producer's finish pass that writes its consumer's operand
+"""The 3D hand-off passes (csrc/s3r_wino_handoff.hip, wino_handoff_kernel): a producer's finish pass that writes its consumer's operand
 — the two-axis plane sets (S3R_LAYOUT_WINO_3D) or [x | Dh | Dd | Ddh] (S3R_LAYOUT_DIFF) — in place of the producer's finish pass
 and the consumer's transform / difference pass.  The four kinds of pair s3r_chain_forward plans:
 
