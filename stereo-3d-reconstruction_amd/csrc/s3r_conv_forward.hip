@@ -1,8 +1,9 @@
 // The forward convolution of libs3r_hip.so's C-ABI (include/s3r.h).  Top to bottom: what every forward convolution shares (ConvCall,
 // the scratch / launch / activation helpers), ONE runner per kernel path (run_*), the dispatcher over them (conv_forward_impl:
 // validation and a switch, no launch), the fused conv + head launch and the chain walker; then ONE extern "C" block of the entry
-// points that are thin fronts for them.  Planning (geometry, kernel policy, sizes, the packed image's layout, the arena) lives in
-// s3r_plan.hip, the profiler in s3r_prof.hip, every other entry point in s3r_api_layers.hip / s3r_api_tasks.hip.  Host code only.
+// points that are thin fronts for them.  Planning lives in the four s3r_plan_*.hip units (geometry; kernel policy, sizes and the packed
+// image's layout; parameter blocks; the arena), the profiler in s3r_prof.hip, every other entry point in s3r_api_layers.hip /
+// s3r_api_tasks.hip.  Host code only.
 #include "s3r_host.h"
 
 #include <algorithm>
@@ -77,9 +78,7 @@ int act_pass(const ConvCall& c, ProfScope& ps, const char* what) {
     return S3R_OK;
 }
 
-// Inputs too large for 32-bit byte offsets go through in sub-batches (a sample's result does not depend on the batch it is computed
-// in, so neither does it on this split): samples [b0, b0 + nb) of the call, x_sample floats of (staged / transformed) input each
-inline int sub_batch(int batch, int b0, int bmax) { return batch - b0 < bmax ? batch - b0 : bmax; }
+// a sub-batch (s3r_host.h, sub_batch): samples [b0, b0 + nb) of the call, x_sample floats of (staged / transformed) input each
 void set_sub_batch(s3r::ConvParams& p, float* y, int b0, int nb, int64_t x_sample) {
     p.B = nb; p.Ntotal = nb * p.Nd * p.Nh * p.Nw;
     p.x_bytes = (unsigned)(4 * (int64_t)nb * x_sample);
@@ -221,7 +220,7 @@ int run_staged(const ConvCall& c) {
     ps.launches = 0;
     const bool in_place = tclass_direct(d);
     const StagedGeo sg = staged_geo(d);
-    int rc = in_place ? S3R_OK : check_scratch(c, (sg.elems + 255) / 256 * 256, "a parameter-general layer stages its input in");
+    int rc = in_place ? S3R_OK : check_scratch(c, align_up(sg.elems, 256), "a parameter-general layer stages its input in");
     if (rc) return rc;
     if (im2col_layer(d)) {
         rc = run_unfolded(c, sg, ps);
@@ -268,13 +267,13 @@ int run_wino1(const ConvCall& c, s3r::ConvParams p, int form, const HeadWork& he
     const bool pre = d->in_layout == S3R_LAYOUT_WINO_H;      // the producer wrote the transformed planes
     const int R = wino_r(d), is3 = d->ndim == 3, n = d->in_size, wp = n + 2, h2 = (n + R - 1) / R, dp = is3 ? n + 2 : 1;
     const int bmax = wino_bmax(d);
-    if (bmax <= 0 || (pre && bmax < d->batch))
+    if (bmax <= 0 || (pre && !fits_one_call(d, ALG_WINO)))
         return fail(S3R_ERR_INVALID, "a Winograd-transformed input takes at most %d samples per call here "
                     "(s3r_conv_wino_input_elems)", bmax);
     const WinoNeed need = wino_need(d, form, false);
     int rc = need.total > 0 ? check_scratch(c, need.total, "the Winograd form of this layer needs") : S3R_OK;
     if (rc) return rc;
-    const int64_t v_sample = wino_v_elems(d) / d->batch, x_sample = g.x_elems / d->batch;
+    const int64_t v_sample = operand_elems(d, S3R_LAYOUT_WINO_H, 1), x_sample = g.x_elems / d->batch;
     ProfScope ps(c.s, F_MFMA, d->tag, g.flops + head.flops, g.bytes + head.bytes);
     wino_prof(ps, c, ALG_WINO, head);
     ps.launches = 0;
@@ -323,7 +322,7 @@ int run_wino2(const ConvCall& c, s3r::ConvParams p, int form, const HeadWork& he
     if (p.out_mode && (g2.ax > 1 || wino2_form_of(d, (int)(g2.pos_sample * d->batch), form) != 0))
         return fail(S3R_ERR_INVALID, "a consumer's operand is written from the class-parallel launch form of a 3D two-axis layer only (the semi-fused "
                     "form of this batch keeps the plain output: s3r_chain_forward plans that itself)");
-    if (g2.bmax <= 0 || ((pre || to_v || p.out_mode) && g2.bmax < d->batch))
+    if (g2.bmax <= 0 || ((pre || to_v || p.out_mode) && !fits_one_call(d, ALG_WINO2)))
         return fail(S3R_ERR_INVALID, "two-axis Winograd form: the transformed input of this batch exceeds 2 GiB (at most %d samples per "
                     "call with a producer-written input: s3r_conv_wino_input_elems)", g2.bmax);
     int rc = check_scratch(c, need.total, "the two-axis Winograd form of this layer needs");
@@ -354,7 +353,7 @@ int run_wino2(const ConvCall& c, s3r::ConvParams p, int form, const HeadWork& he
         hipError_t e = hipSuccess;
         if (!pre) {
             // (aux pass: reads the padded input once, writes its ncls plane sets)
-            s3r::AuxScope aux(c.s, 4.0 * ((double)nb * x_sample + (double)(g2.ax == 2 ? g2.ncls * d->cin * s3r::wino2_npad(g2.pos_sample * nb) : g2.v_sample * nb)));
+            s3r::AuxScope aux(c.s, 4.0 * ((double)nb * x_sample + (double)operand_elems(d, g2.ax == 2 ? S3R_LAYOUT_WINO_HW : S3R_LAYOUT_WINO_3D, nb)));
             if (g2.ax == 2)
                 e = s3r::launch_wino2p_input(c.xf() + (int64_t)b0 * x_sample, c.scratch, nb, d->cin, g2.wp, g2.wp, g2.sg, g2.sg,
                                              s3r::wino2_npad(g2.pos_sample * nb), c.s);

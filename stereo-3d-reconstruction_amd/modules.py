@@ -274,7 +274,7 @@ class _HipChain(nn.Module):
 
     def _has_winograd_form(self, l: spec.Layer) -> bool:
         """Whether the LIBRARY has a Winograd form for this layer at the size it has in this chain (edge >= 4, a transposed
-        layer's edge % 4 == 0, no sigmoid, ...: the rules live in s3r_plan.hip's resolve_algo, so the question is put to the scratch query of a
+        layer's edge % 4 == 0, no sigmoid, ...: the rules live in s3r_plan_algo.hip's resolve_algo, so the question is put to the scratch query of a
         descriptor with algo = WINOGRAD instead of being mirrored here)."""
         if self.precision != "fp32" or l.op not in ("conv2d", "conv3d", "deconv3d"):
             return False

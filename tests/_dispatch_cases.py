@@ -1,4 +1,4 @@
-"""The host-side bookkeeping of the forward dispatcher (csrc/s3r_conv_forward.hip, csrc/s3r_plan.hip), as tests/golden/dispatch_golden.json
+"""The host-side bookkeeping of the forward dispatcher (csrc/s3r_conv_forward.hip, csrc/s3r_plan_*.hip), as tests/golden/dispatch_golden.json
 pins it: size answers and scratch refusals (no GPU), and the profiler records of one forward per kernel path (GPU).
 
 Shared by tests/golden/make_dispatch_golden.py (which writes the file) and tests/test_dispatch_golden_{cpu,gpu}.py (which compare

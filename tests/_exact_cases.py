@@ -365,7 +365,7 @@ THREE_AXIS_RAN = ("winograd-3axis", "winograd-3axis-class-parallel")
 
 
 def three_axis_ran(tile):
-    """s3r_plan.hip, resolve_algo: tile 6 the library's launch form (either), 7 class-parallel, 8 the one-kernel form: both run"""
+    """s3r_plan_algo.hip, resolve_algo: tile 6 the library's launch form (either), 7 class-parallel, 8 the one-kernel form: both run"""
     return {6: THREE_AXIS_RAN, 7: THREE_AXIS_RAN[1:], 8: THREE_AXIS_RAN[:1]}[tile]
 
 

@@ -1,5 +1,5 @@
 """Writes tests/golden/dispatch_golden.json: what the forward dispatcher answers and records (tests/_dispatch_cases.py), taken from
-the build BEFORE a change to csrc/s3r_conv_forward.hip or csrc/s3r_plan.hip that is meant to keep them.
+the build BEFORE a change to csrc/s3r_conv_forward.hip or csrc/s3r_plan_*.hip that is meant to keep them.
 
     python tests/golden/make_dispatch_golden.py --part host          # sizes and scratch refusals: no GPU needed
     python tests/golden/make_dispatch_golden.py --part gpu           # profiler records: on the MI355X

@@ -31,7 +31,7 @@ def test_the_golden_covers_every_entry_point_and_holds_refusals_only(s3r, golden
     block = set(s3r._lib.SIGNATURES) - {"s3r_abi_version", "s3r_last_error", "s3r_conv_out_size", "s3r_conv_packed_elems", "s3r_conv_scratch_elems",
                                         "s3r_chain_workspace_elems", "s3r_conv_wino_input_elems", "s3r_conv_wino_input_layout",
                                         "s3r_profile_enable", "s3r_profile_reset", "s3r_profile_detail", "s3r_profile_read"}
-    assert {row.entry for row in RC.ROWS} == block      # (the others: the version, the message, s3r_plan.hip's queries, the profiler)
+    assert {row.entry for row in RC.ROWS} == block      # (the others: the version, the message, the planner's queries, the profiler)
     for cid, (rc, text) in golden.items():
         assert rc != RC.ERR_HIP, (cid, text)               # a launch was reached
         assert (rc < 0) == (text is not None), cid
