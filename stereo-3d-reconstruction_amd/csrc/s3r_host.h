@@ -91,7 +91,7 @@ struct Plan {
     int64_t total = 0;
 };
 
-// membership in a constexpr table (the layout and bf16-tile whitelists)
+// membership in a constexpr table (the layout whitelists)
 template <int N> inline bool one_of(int v, const int (&table)[N]) {
     for (int t : table)
         if (t == v) return true;

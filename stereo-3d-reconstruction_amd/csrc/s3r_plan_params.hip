@@ -1,6 +1,7 @@
 // Planner, unit 3 of 4 (s3r_host.h): the kernel-side parameter blocks of the direct kernels (fp32, bf16, and the staged /
 // residue-class / depth-to-space views of a parameter-general layer) and their launch forms.  Nothing here enqueues anything.
 #include "s3r_host.h"
+#include "s3r_bf16.h"      // the bf16 tile-code table
 
 #include <cstring>
 
@@ -48,15 +49,13 @@ s3r::ConvParamsH make_params_h(const s3r_conv_desc* d, const Geo& g) {
     return p;
 }
 
-constexpr int kBf16Tiles[] = {1, 2, 3, 4, 5, 6, 9, 10, 17, 18, 19, 20, 21, 22, 23, 40};
-
 int resolve_launch_h(const s3r_conv_desc* d, s3r::ConvParamsH* p, LaunchH* L) {
     const int chunks = d->cin / 32;
     if (d->ksplit < 0 || (d->ksplit > 0 && chunks % d->ksplit != 0))
         return fail(S3R_ERR_INVALID, "ksplit=%d must divide cin/32=%d", d->ksplit, chunks);
     L->ksplit = d->ksplit > 0 ? d->ksplit : s3r::conv_bf16_pick_ksplit(*p);
     p->ksplit = L->ksplit;
-    if (d->tile >= 0 && !one_of(d->tile, kBf16Tiles))
+    if (d->tile >= 0 && !s3r::bf16_tile(d->tile))
         return fail(S3R_ERR_INVALID, "bf16 path: tile must be -1 (auto), 1, 2, 4 (x128 positions, per-tap gather), 3 (128 x 128 couts), 5, 6 "
                     "(x128 positions = 1, 2, plane-reuse gather) or 9, 10 (row-reuse gather); per-tap / plane + 16 = "
                     "32-channel K tiles; 40 (row-persistent e2)");

@@ -14,9 +14,10 @@ MUTANTS = runpy.run_path(os.path.join(ROOT, "tests", "mutants", "table.py"))["MU
 IDS = [m["id"] for m in MUTANTS]
 # what a mutant may not contain: it changes values, never synchronisation, LDS-DMA, launches or assembly
 FORBIDDEN = ["__syncthreads", "waitcnt", "barrier", "buffer_load_lds", "hipLaunchKernelGGL", "asm", "<<<"]
-# (s3r_wino_gemm.hip has no entry of its own: s3r_wino.h's mutants rebuild it, and its serial form is in their kills)
+# (s3r_wino_gemm.hip has no entry of its own: s3r_wino.h's mutants rebuild it, and its serial form is in their kills;
+#  nor has s3r_bf16_plane.hip: s3r_bf16.h's mutant rebuilds it, and its tiles 22 and 6 are in that mutant's kills)
 FILES_NAMED = ["s3r_conv_glds.hip", "s3r_wino.h", "s3r_wino_axis1.hip", "s3r_wino_axis2.hip", "s3r_wino_handoff.hip",
-               "s3r_deconv_wino3.hip", "s3r_conv_bf16.hip", "s3r_pointwise.hip", "s3r_general.hip", "s3r_ordered.h", "s3r_chamfer.hip",
+               "s3r_deconv_wino3.hip", "s3r_bf16.h", "s3r_bf16_tap.hip", "s3r_conv_bf16.hip", "s3r_pointwise.hip", "s3r_general.hip", "s3r_ordered.h", "s3r_chamfer.hip",
                "s3r_disparity.hip", "s3r_batchnorm.hip", "s3r_voxel_loss.hip", "s3r_conv_bwd.hip", "s3r_cost_volume_bwd.hip"]
 
 
@@ -35,7 +36,7 @@ def split_kills(kills):
 
 
 def test_table_shape():
-    assert len(MUTANTS) >= 24
+    assert len(MUTANTS) >= 25
     assert len(set(IDS)) == len(IDS), "mutant ids are not unique"
     for m in MUTANTS:
         assert set(m) <= {"id", "file", "anchor", "replacement", "kills", "models", "equivalent"}, m["id"]
@@ -60,6 +61,7 @@ def test_every_file_is_built_by_the_makefile():
     for m in MUTANTS:
         assert m["file"] in srcs or users(m["file"]), (m["id"], m["file"])
     assert set(users("s3r_wino.h")) == {"s3r_wino_axis1.hip", "s3r_wino_gemm.hip", "s3r_wino_axis2.hip", "s3r_wino_handoff.hip"}
+    assert set(users("s3r_bf16.h")) == {"s3r_bf16_tap.hip", "s3r_bf16_plane.hip", "s3r_conv_bf16.hip", "s3r_plan_params.hip"}
 
 
 @pytest.mark.parametrize("m", MUTANTS, ids=IDS)
